@@ -25,7 +25,20 @@ Modes (the headline line)
   nodeshard   BASELINE C4 shape: the node table split over the ranks, per-pod first keys of every
               shard merged with an RCCL all-reduce(MAX), then decoded (--nodes 100000 --pods 1000000).
 
-With one GPU, rank 0 also measures, after the timed region, and reports as extra keys of the same
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the
+last step's outputs if --dump-outputs is given, and prints the headline line; nothing else runs.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed (the
+arrays a caller receives: node index, score and status per pod) as DIR/idx.npy, DIR/score.npy and
+DIR/status.npy in float64 (every value is an integer below 2^53, so the conversion is exact). The
+inputs are seeded, so two runs with the same arguments write the same arrays.
+
+--full adds everything else to the same line: the check of every buffer against the closed form,
+the device span of the region, the roofline of the dominant kernel (launches of their own), the
+CPU baselines and, with one GPU, the extras below (--no-check, --no-extras and --cpu-seconds 0
+drop single parts of it).
+
+With one GPU and --full, rank 0 also measures, after the timed region, and reports as extra keys of the same
 line: the reference's w = 1 list and MIN-MAX / REVERSE at w = 3 on the same launches; generic_kernel
 (the explicit int64 score per pair, north_star's five stages) on the reference plugin list and on
 NodeNumber + a DEFAULT-normalized score column; the node-table maintenance (f2: msh_patch_nodes and
@@ -144,14 +157,23 @@ def parse():
     ap.add_argument("--mode", choices=["batch", "sequential", "nodeshard"], default="batch")
     ap.add_argument("--nodes", type=int, default=None)
     ap.add_argument("--pods", type=int, default=None, help="pods per GPU (batch/sequential) or total (nodeshard)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary configs (one GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the outputs against the closed form and measure the "
+                         "device span, the roofline, the CPU baselines and the secondary configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/idx.npy, score.npy, status.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="with --full: CPU baseline budget (0 = skip)")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the closed-form check")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the secondary configs (one GPU only)")
     ap.add_argument("--submit", choices=["multi", "single"], default="multi",
                     help="batch mode: the K steps through msh_schedule_batches_device, 32 batches per launch "
                          "(default), or (A/B) one msh_schedule_batch_device launch per step; one host thread "
                          "and one HIP stream either way")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def load_json(path: Path):
@@ -159,6 +181,23 @@ def load_json(path: Path):
         return json.loads(path.read_text())
     except Exception:
         return None
+
+
+DUMP_MAX_BYTES = 60_000_000       # --dump-outputs writes at most this much array data in all (under 64 MB on disk)
+DUMP_SAMPLE_SEED = 0x64756d70      # the rows kept of a larger output: a fixed sample, the same in every run
+
+
+def dump_outputs(out_dir: Path, arrays: dict) -> None:
+    """Write the per-pod output arrays as out_dir/<name>.npy in float64. Outputs over DUMP_MAX_BYTES
+    are cut to a fixed seeded sample of pods (the same sorted rows of every array)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    keep = DUMP_MAX_BYTES // (8 * len(arrays))
+    rows = None
+    if n > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", (a if rows is None else a[rows]).astype(np.float64))
 
 
 class Streams:
@@ -225,8 +264,9 @@ def main():
     msh = importlib.import_module("mini-kube-scheduler_amd")
     synth = importlib.import_module("mini-kube-scheduler_amd.synthetic")
     D = importlib.import_module("mini-kube-scheduler_amd.distributed")
-    sys.path.insert(0, str(ROOT / "tests"))
-    from closed_form import closed_form_modes  # independent checker, not the oracle
+    if args.full:
+        sys.path.insert(0, str(ROOT / "tests"))
+        from closed_form import closed_form_modes  # independent checker, not the oracle
 
     mode = args.mode
     n_total = args.nodes or (100_000 if mode == "nodeshard" else 5_000)
@@ -331,82 +371,99 @@ def main():
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
 
-    # the same K steps again, untimed by the clock, between two events on the launch stream: the
-    # device span of a region (reported beside the wall-clock figure, never as `value`)
-    r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for e in (r0, r1):  # create the HIP events first (a torch Event makes its HIP event on first record)
-        e.record(stream)
-    torch.cuda.synchronize()
-    r0.record(stream)
-    submit(args.steps)
-    r1.record(stream)
-    torch.cuda.synchronize()
-    region_ms = r0.elapsed_time(r1)
-
-    # ---- the dominant kernel's launch duration, for the roofline: R launches back to back on the
-    # stream the kernels run on, each timed by its own start / stop events recorded at the kernel's
-    # start and completion (msh_timing_begin: hipExtLaunchKernelGGL events, the interval rocprofv3's
-    # kernel trace averages); in batch mode the full 32-batch launches of the default submission ----
-    R = 50 if mode != "nodeshard" else min(args.steps, 20)
-    ctx.timing_begin(R)
-    for _ in range(R):
-        if mode == "batch" and multi:
-            rc = fast.schedule_batches_device(handle, G, descs_addr, sh or None)
-            if rc:
-                ctx._check(rc)
-        elif mode == "batch":
-            rc = fast.schedule_batch_device(*batch_args[0])
-            if rc:
-                ctx._check(rc)
-        elif mode == "sequential":
-            b = bufs[0]
-            ctx.schedule_sequential_device(p, b["pd"].data_ptr(), b["pt"].data_ptr(), 0, b["idx"].data_ptr(),
-                                           b["score"].data_ptr(), b["status"].data_ptr(), sh)
-        else:
-            b = bufs[0]
-            ctx.shard_keys_device(p, b["pd"].data_ptr(), b["pt"].data_ptr(), node_base, b["keys"].data_ptr(), sh)
-    n_timed, tot_ms, max_ms = ctx.timing_end()
-    launch_ms = tot_ms / max(n_timed, 1)
-    batches_per_launch = G if (mode == "batch" and multi) else 1
-    if mode == "nodeshard":  # the timed steps hold the all-reduce and the decode too: redo them after
-        submit(1)
-        torch.cuda.synchronize()
-
     if world > 1:
-        t = torch.tensor([elapsed, launch_ms, region_ms], dtype=torch.float64, device=dev)
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, launch_ms, region_ms = float(t[0]), float(t[1]), float(t[2])
+        elapsed = float(t[0])
 
-    # ---- correctness of every buffer's last batch against the independent closed form ----
-    check = "skipped"
-    if rank == 0 and not args.no_check:
-        ok = True
-        for (pod_digit, pod_tol), b in zip(batches, bufs):
-            want = closed_form_modes(unsched, node_digit, pod_digit, pod_tol, HEADLINE_WEIGHT, HEADLINE_NORM)
-            got = (b["idx"].cpu().numpy(), b["score"].cpu().numpy(), b["status"].cpu().numpy())
-            ok = ok and all((g == w).all() for g, w in zip(got, want))
-        check = "bit-exact vs closed form" if ok else "MISMATCH"
+    # ---- what the last timed step computed (step K - 1 wrote buffer (K - 1) mod the buffer count), read
+    # before anything else is launched ----
+    if args.dump_outputs and rank == 0:
+        last = bufs[(args.steps - 1) % len(bufs)]
+        dump_outputs(Path(args.dump_outputs), {k: last[k].cpu().numpy() for k in ("idx", "score", "status")})
 
-    n_local = ctx.n_nodes
     evals_total = float(n_total) * float(p if mode != "nodeshard" else p_total) * args.steps * (world if mode != "nodeshard" else 1)
     pods_total = float(p) * args.steps * (world if mode != "nodeshard" else 1)
     value = evals_total / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
 
-    roofline = make_roofline(mode, n_local, p, launch_ms, batches_per_launch, cus)
-    roofline["region_device_ms_per_step"] = region_ms / args.steps
+    def full_report() -> dict:
+        """What --full adds to the line, from runs of their own after the timed region."""
+        # the same K steps again, untimed by the clock, between two events on the launch stream: the
+        # device span of a region (reported beside the wall-clock figure, never as `value`)
+        r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for e in (r0, r1):  # create the HIP events first (a torch Event makes its HIP event on first record)
+            e.record(stream)
+        torch.cuda.synchronize()
+        r0.record(stream)
+        submit(args.steps)
+        r1.record(stream)
+        torch.cuda.synchronize()
+        region_ms = r0.elapsed_time(r1)
 
-    extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
-        extras = measure_extras(torch, dev, msh, synth, D, closed_form_modes, cus)
+        # ---- the dominant kernel's launch duration, for the roofline: R launches back to back on the
+        # stream the kernels run on, each timed by its own start / stop events recorded at the kernel's
+        # start and completion (msh_timing_begin: hipExtLaunchKernelGGL events, the interval rocprofv3's
+        # kernel trace averages); in batch mode the full 32-batch launches of the default submission ----
+        R = 50 if mode != "nodeshard" else min(args.steps, 20)
+        ctx.timing_begin(R)
+        for _ in range(R):
+            if mode == "batch" and multi:
+                rc = fast.schedule_batches_device(handle, G, descs_addr, sh or None)
+                if rc:
+                    ctx._check(rc)
+            elif mode == "batch":
+                rc = fast.schedule_batch_device(*batch_args[0])
+                if rc:
+                    ctx._check(rc)
+            elif mode == "sequential":
+                b = bufs[0]
+                ctx.schedule_sequential_device(p, b["pd"].data_ptr(), b["pt"].data_ptr(), 0, b["idx"].data_ptr(),
+                                               b["score"].data_ptr(), b["status"].data_ptr(), sh)
+            else:
+                b = bufs[0]
+                ctx.shard_keys_device(p, b["pd"].data_ptr(), b["pt"].data_ptr(), node_base, b["keys"].data_ptr(), sh)
+        n_timed, tot_ms, max_ms = ctx.timing_end()
+        launch_ms = tot_ms / max(n_timed, 1)
+        batches_per_launch = G if (mode == "batch" and multi) else 1
+        if mode == "nodeshard":  # the timed steps hold the all-reduce and the decode too: redo them after
+            submit(1)
+            torch.cuda.synchronize()
 
-    cpu = cpu_omp = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:  # the contract: rank 0 at N=1 only
-        pod_digit, pod_tol = batches[0]
-        cpu = cpu_baseline(unsched, node_digit, pod_digit, pod_tol, args.cpu_seconds, mode)
-        if mode != "sequential":
-            cpu_omp = cpu_baseline(unsched, node_digit, pod_digit, pod_tol, args.cpu_seconds / 2, mode,
-                                   threads=host_cpu_share())
+        if world > 1:
+            t = torch.tensor([launch_ms, region_ms], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            launch_ms, region_ms = float(t[0]), float(t[1])
+
+        # ---- correctness of every buffer's last batch against the independent closed form ----
+        check = "skipped"
+        if rank == 0 and not args.no_check:
+            ok = True
+            for (pod_digit, pod_tol), b in zip(batches, bufs):
+                want = closed_form_modes(unsched, node_digit, pod_digit, pod_tol, HEADLINE_WEIGHT, HEADLINE_NORM)
+                got = (b["idx"].cpu().numpy(), b["score"].cpu().numpy(), b["status"].cpu().numpy())
+                ok = ok and all((g == w).all() for g, w in zip(got, want))
+            check = "bit-exact vs closed form" if ok else "MISMATCH"
+
+        n_local = ctx.n_nodes
+        roofline = make_roofline(mode, n_local, p, launch_ms, batches_per_launch, cus)
+        roofline["region_device_ms_per_step"] = region_ms / args.steps
+
+        extras = {}
+        if rank == 0 and world == 1 and not args.no_extras:
+            extras = measure_extras(torch, dev, msh, synth, D, closed_form_modes, cus)
+
+        cpu = cpu_omp = None
+        if rank == 0 and world == 1 and args.cpu_seconds > 0:  # the contract: rank 0 at N=1 only
+            pod_digit, pod_tol = batches[0]
+            cpu = cpu_baseline(unsched, node_digit, pod_digit, pod_tol, args.cpu_seconds, mode)
+            if mode != "sequential":
+                cpu_omp = cpu_baseline(unsched, node_digit, pod_digit, pod_tol, args.cpu_seconds / 2, mode,
+                                       threads=host_cpu_share())
+
+        return {"check": check, "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_omp": cpu_omp, **extras}
+
+    full = full_report() if args.full else {}
 
     if rank == 0:
         if mode == "batch":
@@ -439,12 +496,8 @@ def main():
                        else "per step",
                        **({"rehearsal": "all ranks on cuda:0, gloo (not a measurement)"} if rehearse else {})},
             "pods_per_s": pods_total / elapsed,
-            "check": check,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "cpu_baseline_omp": cpu_omp,
         }
-        line.update(extras)
+        line.update(full)
         print(json.dumps(line), flush=True)
     ctx.close()
     if world > 1:
