@@ -149,6 +149,35 @@ func (x *Ctx) Close() {
 	runtime.SetFinalizer(x, nil)
 }
 
+// TieBreak is selectHost's choice among the maximum-score nodes (msh_tiebreak).
+type TieBreak int32
+
+const (
+	TieBreakFirst  TieBreak = C.MSH_TIEBREAK_FIRST  // the first maximum in List order (the default)
+	TieBreakRandom TieBreak = C.MSH_TIEBREAK_RANDOM // uniform among the maxima, as the reference's reservoir scan
+)
+
+// SetTieBreak selects the tie-break of the batch calls (ScheduleBatch, Submit). TieBreakRandom places a
+// pod on a uniformly drawn node of its tie set (minisched.go:304-325's distribution), the draw being
+// SplitMix64(seed) at counter + the pod's position in the batch; each batch advances the counter by its
+// pod count. ScheduleSequential, ScheduleNodeShard and Group.ScheduleBatch fail in that mode.
+func (x *Ctx) SetTieBreak(mode TieBreak, seed, counter uint64) error {
+	if rc := C.msh_set_tiebreak(x.c, C.int32_t(mode), C.uint64_t(seed), C.uint64_t(counter)); rc != C.MSH_OK {
+		return x.lastErr("msh_set_tiebreak", rc)
+	}
+	return nil
+}
+
+// TieBreak returns the mode, the seed and the live draw counter (checkpoint it to replay a batch).
+func (x *Ctx) TieBreak() (mode TieBreak, seed, counter uint64, err error) {
+	var m C.int32_t
+	var s, c C.uint64_t
+	if rc := C.msh_get_tiebreak(x.c, &m, &s, &c); rc != C.MSH_OK {
+		return TieBreakFirst, 0, 0, x.lastErr("msh_get_tiebreak", rc)
+	}
+	return TieBreak(m), uint64(s), uint64(c), nil
+}
+
 // UploadNodes replaces the per-cycle Nodes().List (minisched.go:40): the nodes are put in List
 // order (byte-sorted names, the apiserver's etcd key order) and their two columns uploaded.
 // It returns the device-index -> node mapping, also kept for ScheduleBatch.

@@ -29,8 +29,13 @@
  *  - Node tables are in the reference's LIST order: byte-wise sorted node names
  *    (etcd key order, minisched.go:40). msh_pack_nodes produces that order.
  *  - Tie-break: the reference's selectHost reservoir-samples ties with math/rand
- *    (minisched.go:316-321). This library's contract is deterministic: the
+ *    (minisched.go:316-321), so every node with the maximum total is equally likely. A ctx has
+ *    two modes (msh_set_tiebreak). MSH_TIEBREAK_FIRST, the default, is deterministic: the
  *    LOWEST node index among the maximum total score (first max in List order).
+ *    MSH_TIEBREAK_RANDOM picks uniformly among the maxima from a seeded, counter-based draw:
+ *    the same distribution as the reservoir scan, reproducible from (seed, counter). It is not
+ *    the same stream as Go's global math/rand, which depends on the process's whole call
+ *    history and cannot be reproduced without Go.
  */
 #ifndef MINISCHED_HIP_H
 #define MINISCHED_HIP_H
@@ -152,6 +157,39 @@ int msh_set_plugins_ex(msh_ctx* ctx, const int32_t* filter_ids, int32_t nf,
                        const int32_t* prescore_ids, int32_t npre,
                        const int32_t* score_ids, const int64_t* weights,
                        const int32_t* normalize, int32_t ns);
+
+/* ---- tie-break among the maximum totals (added after v8, additive) ----
+ * MSH_TIEBREAK_FIRST: the first maximum in List order (the default; what every earlier version does).
+ * MSH_TIEBREAK_RANDOM, for a pod whose status is MSH_PLACED:
+ *   tie set  T = the feasible nodes whose total equals the pod's maximum total, in List order, c = |T|;
+ *   choice   the pod goes to the k-th node of T (0-based), k = (u * c) >> 32 in 64 bits (c < 2^24);
+ *   draw     u = the high 32 bits of SplitMix64 at position `counter`:
+ *              z = seed + (counter + 1) * 0x9E3779B97F4A7C15      (mod 2^64)
+ *              z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *              z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *              z =  z ^ (z >> 31);   u = z >> 32
+ *   counter  pod j of a call draws at base + j, base = the ctx's draw counter when the call is
+ *            submitted (async and _device calls included); the call then advances the counter by p,
+ *            whatever the pods' statuses. In msh_schedule_batches_device batch i starts where batch
+ *            i - 1 ended.
+ * out_score and out_status are exactly FIRST mode's: the tie-break only chooses among equal totals. The
+ * choice is uniform over T up to a bias below c / 2^32.
+ * msh_get_tiebreak returns the live counter: a caller checkpoints (seed, counter) and replays a batch,
+ * or gives a pod-sharded rank counter = the index of its first pod, and that rank places its slice
+ * exactly as one GPU would place it within the whole batch.
+ * RANDOM is honoured by msh_schedule_batch, msh_schedule_batch_async, msh_schedule_batch_device and
+ * msh_schedule_batches_device, for every plugin list without a score column (with or without the
+ * NodeUnschedulable filter, NodeNumber in or out of the prescore and score lists, every normalize mode,
+ * every weight). While the ctx is in RANDOM mode these return MSH_ERR_UNSUPPORTED (the message names
+ * the entry point), do no device work and leave the counter alone: msh_schedule_sequential and
+ * msh_schedule_sequential_device; msh_shard_keys_device, msh_decode_keys_device and the
+ * msh_generic_*_device entry points; msh_schedule_nodeshard and msh_schedule_nodeshard_device;
+ * msh_group_schedule_batch when any shard is in RANDOM mode; a batch whose score list names a score
+ * column; and every batch of a ctx created with msh_options.batch_kernel = 1.
+ * msh_set_tiebreak: a mode outside the enum is MSH_ERR_INVALID. */
+typedef enum msh_tiebreak { MSH_TIEBREAK_FIRST = 0, MSH_TIEBREAK_RANDOM = 1 } msh_tiebreak;
+int msh_set_tiebreak(msh_ctx* ctx, int32_t mode, uint64_t seed, uint64_t counter);
+int msh_get_tiebreak(const msh_ctx* ctx, int32_t* out_mode, uint64_t* out_seed, uint64_t* out_counter);
 
 /* Node table in List order (name-sorted). unsched[i] = node.Spec.Unschedulable (0/1);
  * digit[i] = last byte of node.Name as '0'..'9' -> 0..9, else -1 (nodenumber.go:81-87).

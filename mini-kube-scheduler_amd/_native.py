@@ -47,10 +47,13 @@ MSH_NORMALIZE_DEFAULT = 1
 MSH_NORMALIZE_DEFAULT_REVERSE = 2
 MSH_NORMALIZE_MINMAX = 3
 
+MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
+MSH_TIEBREAK_RANDOM = 1  # seeded uniform choice among the maxima (msh_set_tiebreak)
+
 # Every symbol include/minisched_hip.h declares (checked by tests/test_abi.py).
 EXPORTED = (
     "msh_abi_version", "msh_device_count", "msh_host_alloc", "msh_host_free", "msh_create", "msh_create_ex",
-    "msh_destroy", "msh_last_error",
+    "msh_destroy", "msh_last_error", "msh_set_tiebreak", "msh_get_tiebreak",
     "msh_set_plugins", "msh_set_plugins_ex", "msh_upload_nodes", "msh_upload_score_column", "msh_num_nodes",
     "msh_patch_nodes", "msh_export_results",
     "msh_schedule_batch", "msh_schedule_batch_async", "msh_wait", "msh_schedule_batch_device",
@@ -140,6 +143,8 @@ _SIGS = {
     "msh_create_ex": (C.c_int, [C.c_int, C.POINTER(Options), C.POINTER(_P)]),
     "msh_destroy": (None, [_P]),
     "msh_last_error": (C.c_char_p, [_P]),
+    "msh_set_tiebreak": (C.c_int, [_P, _I32, C.c_uint64, C.c_uint64]),
+    "msh_get_tiebreak": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "msh_set_plugins": (C.c_int, [_P, _P, _I32, _P, _P, _I32]),
     "msh_set_plugins_ex": (C.c_int, [_P, _P, _I32, _P, _I32, _P, _P, _P, _I32]),
     "msh_upload_nodes": (C.c_int, [_P, _I32, _P, _P]),

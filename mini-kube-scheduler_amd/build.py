@@ -29,6 +29,7 @@ ARCH = os.environ.get("MSH_OFFLOAD_ARCH", "gfx950")
 SOURCES = [
     # (source, compiler, extra flags): one translation unit per kernel family, compiled in parallel
     ("msh_pair.hip", "hipcc", ["-x", "hip"]),
+    ("msh_tiebreak.hip", "hipcc", ["-x", "hip"]),
     ("msh_generic.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_cap.hip", "hipcc", ["-x", "hip"]),

@@ -443,7 +443,52 @@ msh::PairArgs pair_args(msh_ctx* c) {
 int launch_generic_descs(msh_ctx* c, const msh::BatchDesc* d, int32_t nb, hipStream_t s);
 bool use_generic(const msh_ctx* c);
 
+// The refusals of MSH_TIEBREAK_RANDOM (include/minisched_hip.h): the random tie-break runs on the bit-plane
+// batch path only. generic: the ctx's batches run on generic_kernel (a score column, or batch_kernel = 1).
+int random_unsupported(msh_ctx* c, const char* entry, bool generic) {
+  return fail(c, MSH_ERR_UNSUPPORTED,
+              std::string(entry) + ": MSH_TIEBREAK_RANDOM is not implemented " +
+                  (generic ? "for score-column plugin lists and msh_options.batch_kernel = 1" : "for this entry point") +
+                  " (msh_set_tiebreak(ctx, MSH_TIEBREAK_FIRST, 0, 0) restores the first maximum)");
+}
+
+int refuse_random(msh_ctx* c, const char* entry) {
+  return c->tiebreak_mode == MSH_TIEBREAK_RANDOM ? random_unsupported(c, entry, false) : MSH_OK;
+}
+
+// A batch entry point in RANDOM mode on a ctx whose batches run on generic_kernel: refused up front.
+int refuse_random_generic(msh_ctx* c, const char* entry) {
+  return c->tiebreak_mode == MSH_TIEBREAK_RANDOM && use_generic(c) ? random_unsupported(c, entry, true) : MSH_OK;
+}
+
+// RANDOM mode: nb batches on pair_pick_kernel (msh_tiebreak.hip), MULTI_MAX per launch; batch i draws where
+// batch i - 1 ended, and the ctx's counter advances by the pods of every batch launched.
+int launch_pick_descs(msh_ctx* c, const msh::BatchDesc* d, int32_t nb, hipStream_t s) {
+  if (use_generic(c)) return random_unsupported(c, "the batch entry points", true);
+  for (int32_t i0 = 0; i0 < nb; i0 += msh::MULTI_MAX) {
+    const int n = std::min<int32_t>(msh::MULTI_MAX, nb - i0);
+    TimedLaunch tl(c);
+    msh::PickArgs a{};
+    a.planes = cur_table(c).d_planes;
+    a.n_groups = c->n_pad / msh::GROUP_NODES;
+    a.nb = n;
+    a.pp = c->pp;
+    a.seed = c->tie_seed;
+    uint64_t base = c->tie_counter;
+    for (int k = 0; k < n; ++k) {
+      a.d[k] = d[i0 + k];
+      a.draw_base[k] = base;
+      base += (uint64_t)d[i0 + k].n_pods;
+    }
+    const hipError_t e = msh::launch_pair_pick(a, s);
+    if (e != hipSuccess) return hip_fail(c, e, "pair_pick_kernel");
+    c->tie_counter = base;
+  }
+  return MSH_OK;
+}
+
 int launch_batch_descs(msh_ctx* c, const msh::BatchDesc* d, int32_t nb, hipStream_t s) {
+  if (c->tiebreak_mode == MSH_TIEBREAK_RANDOM) return launch_pick_descs(c, d, nb, s);
   if (use_generic(c)) return launch_generic_descs(c, d, nb, s);
   for (int32_t i0 = 0; i0 < nb; i0 += msh::MULTI_MAX) {
     const int n = std::min<int32_t>(msh::MULTI_MAX, nb - i0);
@@ -818,6 +863,25 @@ int msh_set_plugins_ex(msh_ctx* c, const int32_t* filter_ids, int32_t nf,
   return MSH_OK;
 }
 
+int msh_set_tiebreak(msh_ctx* c, int32_t mode, uint64_t seed, uint64_t counter) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (mode != MSH_TIEBREAK_FIRST && mode != MSH_TIEBREAK_RANDOM)
+    return fail(c, MSH_ERR_INVALID, "tie-break mode " + std::to_string(mode) + ": not MSH_TIEBREAK_FIRST (0) or MSH_TIEBREAK_RANDOM (1)");
+  c->tiebreak_mode = mode;
+  c->tie_seed = seed;
+  c->tie_counter = counter;
+  return MSH_OK;
+}
+
+int msh_get_tiebreak(const msh_ctx* c, int32_t* out_mode, uint64_t* out_seed, uint64_t* out_counter) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_mode) *out_mode = c->tiebreak_mode;
+  if (out_seed) *out_seed = c->tie_seed;
+  if (out_counter) *out_counter = c->tie_counter;
+  return MSH_OK;
+}
+
 int msh_set_plugins(msh_ctx* c, const int32_t* filter_ids, int32_t nf, const int32_t* score_ids,
                     const int64_t* weights, int32_t ns) {
   // NodeNumber implements PreScore too (nodenumber.go:50), so it is its own prescore plugin.
@@ -941,10 +1005,11 @@ int msh_schedule_batch_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // d_out_score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
+  int rc = refuse_random_generic(c, "msh_schedule_batch_device");
+  if (rc != MSH_OK) return rc;
   DeviceGuard g(c->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = ready(c);
-  if (rc != MSH_OK) return rc;
+  if ((rc = ready(c)) != MSH_OK) return rc;
   if (p == 0) return MSH_OK;
   const msh::BatchDesc d{d_pod_digit, d_pod_tol, d_out_idx, d_out_score, d_out_status, p, 0};
   if ((rc = launch_batch_descs(c, &d, 1, s)) != MSH_OK) return rc;
@@ -962,10 +1027,11 @@ int msh_schedule_batches_device(msh_ctx* c, int32_t nb, const msh_batch* batches
     if (b.p > 0 && (!b.pod_digit || !b.pod_tol || !b.out_idx || !b.out_status))  // out_score optional
       return fail(c, MSH_ERR_INVALID, "batch " + std::to_string(i) + ": null device pointer");
   }
+  int rc = refuse_random_generic(c, "msh_schedule_batches_device");
+  if (rc != MSH_OK) return rc;
   DeviceGuard g(c->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = ready(c);
-  if (rc != MSH_OK) return rc;
+  if ((rc = ready(c)) != MSH_OK) return rc;
   for (int32_t i0 = 0; i0 < nb; i0 += msh::MULTI_MAX) {  // MULTI_MAX batches per launch
     const int32_t n = std::min<int32_t>(msh::MULTI_MAX, nb - i0);
     msh::BatchDesc d[msh::MULTI_MAX];
@@ -985,11 +1051,12 @@ int msh_schedule_batch(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uin
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // out_score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
+  int rc = refuse_random_generic(c, "msh_schedule_batch");
+  if (rc != MSH_OK) return rc;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
-  int rc = ready(c);
-  if (rc != MSH_OK) return rc;
+  if ((rc = ready(c)) != MSH_OK) return rc;
   HostIO io;
   if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
   rc = msh_schedule_batch_device(c, p, io.d_pd, io.d_pt, io.o_idx, io.o_score, io.o_status, c->stream);
@@ -1005,6 +1072,8 @@ int msh_schedule_batch_async(msh_ctx* c, int32_t p, const int8_t* pod_digit, con
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // out_score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
+  int rc = refuse_random_generic(c, "msh_schedule_batch_async");
+  if (rc != MSH_OK) return rc;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
   DeviceGuard g(c->device);
   void *dpd = nullptr, *dpt = nullptr, *doi = nullptr, *dos = nullptr, *dost = nullptr;
@@ -1017,8 +1086,7 @@ int msh_schedule_batch_async(msh_ctx* c, int32_t p, const int8_t* pod_digit, con
     if (!dpd || !dpt || !doi || !dost || (out_score && !dos))
       return fail(c, MSH_ERR_INVALID, "msh_schedule_batch_async needs page-locked buffers (msh_host_alloc)");
   }
-  int rc = ready(c);
-  if (rc != MSH_OK) return rc;
+  if ((rc = ready(c)) != MSH_OK) return rc;
   if (c->async_issued - c->async_done >= MSH_ASYNC_DEPTH) {  // the ring is full: wait for the oldest
     const uint64_t t = c->async_done + 1;
     MSH_HIP(c, hipEventSynchronize(c->async_ev[t % MSH_ASYNC_DEPTH]));
@@ -1057,11 +1125,12 @@ int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_di
   if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // d_out_score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
+  int rc = refuse_random(c, "msh_schedule_sequential_device");
+  if (rc != MSH_OK) return rc;
   if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
   DeviceGuard g(c->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc = ready(c);
-  if (rc != MSH_OK) return rc;
+  if ((rc = ready(c)) != MSH_OK) return rc;
   msh::SeqArgs a{};
   const NodeTable& t = cur_table(c);
   a.planes = t.d_planes;
@@ -1121,11 +1190,12 @@ int msh_schedule_sequential(msh_ctx* c, int32_t p, const int8_t* pod_digit, cons
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // out_score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
+  int rc = refuse_random(c, "msh_schedule_sequential");
+  if (rc != MSH_OK) return rc;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
-  int rc = ready(c);
-  if (rc != MSH_OK) return rc;
+  if ((rc = ready(c)) != MSH_OK) return rc;
   HostIO io;
   if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
   rc = msh_schedule_sequential_device(c, p, io.d_pd, io.d_pt, max_pods_per_node, io.o_idx, io.o_score,
@@ -1194,6 +1264,7 @@ int msh_shard_keys_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
   c->err.clear();
   if (p < 0 || node_base < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_keys)) return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (int rr = refuse_random(c, "msh_shard_keys_device"); rr != MSH_OK) return rr;
   if (node_base + (int64_t)c->n_nodes >= msh::GKEY_MAX) return fail(c, MSH_ERR_INVALID, "global node index overflows the key");
   if (c->generic)
     return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugin lists shard through msh_generic_extents_device / "
@@ -1225,6 +1296,7 @@ int msh_decode_keys_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_keys || !d_out_idx || !d_out_status))  // d_out_score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (int rr = refuse_random(c, "msh_decode_keys_device"); rr != MSH_OK) return rr;
   DeviceGuard g(c->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipError_t e = msh::launch_decode_keys(d_pod_digit, p, d_keys, c->pp, d_out_idx, d_out_score, d_out_status, s);
@@ -1272,6 +1344,7 @@ int msh_generic_extents_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
   if (!c) return MSH_ERR_INVALID;
   c->err.clear();
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
+  if (int rr = refuse_random(c, "msh_generic_extents_device"); rr != MSH_OK) return rr;
   int64_t len = 0;
   msh_generic_ext_len(c, p, &len);
   if (p == 0 || len == 0) return MSH_OK;  // no plugin normalizes: nothing to merge
@@ -1291,6 +1364,7 @@ int msh_generic_best_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, co
   if (p < 0 || node_base < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (node_base + (int64_t)c->n_nodes >= (int64_t)INT32_MAX)
     return fail(c, MSH_ERR_INVALID, "global node index overflows int32");
+  if (int rr = refuse_random(c, "msh_generic_best_device"); rr != MSH_OK) return rr;
   int64_t len = 0;
   msh_generic_ext_len(c, p, &len);
   if (p == 0) return MSH_OK;
@@ -1309,6 +1383,7 @@ int msh_generic_candidates_device(msh_ctx* c, int32_t p, const int64_t* d_local_
   c->err.clear();
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!d_local_total || !d_merged_total || !d_best_idx)) return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (int rr = refuse_random(c, "msh_generic_candidates_device"); rr != MSH_OK) return rr;
   DeviceGuard g(c->device);
   hipError_t e = msh::launch_generic_candidates(p, d_local_total, d_merged_total, d_best_idx,
                                                 reinterpret_cast<hipStream_t>(stream));
@@ -1324,6 +1399,7 @@ int msh_generic_decode_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, 
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!d_pod_digit || !d_merged_total || !d_merged_idx || !d_out_idx || !d_out_status))
     return fail(c, MSH_ERR_INVALID, "null device pointer");  // d_out_score optional
+  if (int rr = refuse_random(c, "msh_generic_decode_device"); rr != MSH_OK) return rr;
   DeviceGuard g(c->device);
   int32_t nn_score = 0;
   for (int32_t id : c->score_ids) nn_score |= id == MSH_PLUGIN_NODE_NUMBER ? 1 : 0;

@@ -54,6 +54,10 @@ struct msh_ctx {
   std::vector<int32_t> filter_ids, prescore_ids, score_ids, normalize;
   std::vector<int64_t> weights;
   msh::PluginParams pp{1, 1, 1, 0, 1};
+  // tie-break among the maximum totals (msh_set_tiebreak): the mode, and in RANDOM mode the seed and
+  // the position of the next batch's first draw (advanced by p at each batch submission)
+  int32_t tiebreak_mode = MSH_TIEBREAK_FIRST;
+  uint64_t tie_seed = 0, tie_counter = 0;
 
   // node table: two versions. Launches read tab[cur]; a rewrite (upload, patch, plugin change,
   // score column) builds the other version on prep_stream and then publishes it, so it never waits
@@ -134,6 +138,9 @@ int generic_args(msh_ctx* c, msh::GenericArgs& g);
 // The generic pipeline runs the batch entry points when the score list names a score column (or for
 // every list with msh_options.batch_kernel = 1).
 bool use_generic(const msh_ctx* c);
+// MSH_OK in MSH_TIEBREAK_FIRST mode; in RANDOM mode MSH_ERR_UNSUPPORTED with a message naming `entry`, an
+// entry point the random tie-break does not cover (checked before any device work).
+int refuse_random(msh_ctx* c, const char* entry);
 
 // One hot-kernel launch under msh_timing_begin: arms the next event pair for the launcher on this
 // thread; a launcher that launched nothing leaves it unused.

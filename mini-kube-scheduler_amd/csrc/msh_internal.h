@@ -151,6 +151,23 @@ struct PairArgsN : PairCommon {
 using PairArgs = PairArgsN<MULTI_MAX>;
 hipError_t launch_pairs(PairArgs& a, bool shard, const DeviceInfo& dev, hipStream_t s);
 
+// MSH_TIEBREAK_RANDOM (msh_tiebreak.hip, pair_pick_kernel): nb (1..MULTI_MAX) batches in one launch; pod j
+// of batch b draws at position draw_base[b] + j of the SplitMix64 stream seeded with `seed`.
+struct PickArgs {
+  const uint32_t* planes;  // bit-sliced node table (PLANE_* layout), n_groups groups
+  int32_t n_groups;
+  int32_t nb;
+  PluginParams pp;
+  uint64_t seed;
+  BatchDesc d[MULTI_MAX];
+  uint64_t draw_base[MULTI_MAX];
+};
+// The planes are staged in LDS up to this many groups, launch_pairs' limit for pair_lds_kernel
+// (PAIR_LDS_BIG_GROUPS, msh_pair.hip: 106,496 nodes, 78 KB per workgroup); larger tables are read from
+// global memory.
+constexpr int TIEBREAK_LDS_MAX_GROUPS = 416;
+hipError_t launch_pair_pick(const PickArgs& a, hipStream_t s);
+
 hipError_t launch_decode_keys(const int8_t* pod_digit, int32_t p, const int32_t* keys, PluginParams pp,
                               int32_t* out_idx, int64_t* out_score, int32_t* out_status, hipStream_t s);
 

@@ -392,6 +392,7 @@ int msh_schedule_nodeshard_device(msh_ctx* c, int32_t p, const int8_t* d_pod_dig
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // d_out_score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (int rr = refuse_random(c, "msh_schedule_nodeshard_device"); rr != MSH_OK) return rr;
   DeviceGuard g(c->device);
   return nodeshard(c, p, d_pod_digit, d_pod_tol, node_base, d_out_idx, d_out_score, d_out_status,
                    reinterpret_cast<hipStream_t>(stream));
@@ -404,6 +405,7 @@ int msh_schedule_nodeshard(msh_ctx* c, int32_t p, const int8_t* pod_digit, const
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // out_score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
+  if (int rr = refuse_random(c, "msh_schedule_nodeshard"); rr != MSH_OK) return rr;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
   DeviceGuard g(c->device);
   if (p == 0) return nodeshard(c, 0, nullptr, nullptr, node_base, nullptr, nullptr, nullptr, c->stream);
@@ -505,6 +507,10 @@ int msh_group_schedule_batch(msh_group* g, int32_t p, const int8_t* pod_digit, c
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status)) return gfail(g, MSH_ERR_INVALID, "null host pointer");
   const size_t n = g->shards.size();
   msh_ctx* home = g->shards[0];
+  for (size_t k = 0; k < n; ++k)  // the sharded forms would need a count all-reduce: first maximum only
+    if (g->shards[k]->tiebreak_mode == MSH_TIEBREAK_RANDOM)
+      return gfail(g, MSH_ERR_UNSUPPORTED, "msh_group_schedule_batch: shard " + std::to_string(k) +
+                                               " is in MSH_TIEBREAK_RANDOM mode, which is not implemented for device groups");
   // the slices' global bases, and one plugin configuration for the whole group
   std::vector<int64_t> base(n);
   int64_t total_nodes = 0;

@@ -127,13 +127,31 @@ class NodeShardedScheduler:
 class PodShardedScheduler:
     """Pod-sharded batch (or sequential) scheduling: full node table, this rank's pods."""
 
-    def __init__(self, ctx, unsched: np.ndarray, digit: np.ndarray, world: int, rank: int, group=None):
+    def __init__(self, ctx, unsched: np.ndarray, digit: np.ndarray, world: int, rank: int, group=None, *,
+                 tie_break="first", tie_seed: int = 0):
         self.ctx = ctx
         self.world, self.rank, self.group = world, rank, group
         ctx.upload_nodes(unsched, digit)
+        # tie_break="random": every rank draws from the one stream of the whole batch, pod j at position j,
+        # so the ranks together place the pods exactly as one GPU would (begin_batch sets the counter)
+        self.random = tie_break in ("random", 1)
+        self.tie_seed = int(tie_seed)
+        self.drawn = 0  # pods of the batches begun so far (the whole batches, every rank's slices)
+        if self.random:
+            ctx.set_tiebreak("random", self.tie_seed, 0)
 
     def pod_range(self, p_total: int) -> tuple[int, int]:
         return shard_range(p_total, self.world, self.rank)
+
+    def begin_batch(self, p_total: int) -> tuple[int, int]:
+        """This rank's pod_range of the next batch of p_total pods; with tie_break="random" the ctx's draw
+        counter is first set to the global index of the slice's first pod. Call it once per batch, on
+        every rank, before scheduling the slice."""
+        lo, hi = self.pod_range(p_total)
+        if self.random:
+            self.ctx.set_tiebreak("random", self.tie_seed, self.drawn + lo)
+            self.drawn += p_total
+        return lo, hi
 
     def merge_node_counts(self, counts):
         """Sequential mode: the commit state (pods per node) summed over ranks. Exact only when

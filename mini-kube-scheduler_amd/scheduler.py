@@ -31,6 +31,10 @@ SCORE_IDS = {NODE_NUMBER: N.MSH_PLUGIN_NODE_NUMBER,
 # Only NodeNumber implements PreScore (nodenumber.go:50-64); a score column has none, so naming one in
 # the prescore list is MSH_ERR_UNSUPPORTED here exactly as in msh_set_plugins_ex.
 PRESCORE_IDS = {NODE_NUMBER: N.MSH_PLUGIN_NODE_NUMBER}
+# msh_tiebreak by name and by value (DeviceContext.set_tiebreak, Scheduler(tie_break=...))
+TIEBREAK_MODES = {"first": N.MSH_TIEBREAK_FIRST, "random": N.MSH_TIEBREAK_RANDOM,
+                  N.MSH_TIEBREAK_FIRST: N.MSH_TIEBREAK_FIRST, N.MSH_TIEBREAK_RANDOM: N.MSH_TIEBREAK_RANDOM}
+_U64 = (1 << 64) - 1
 
 
 @dataclass(frozen=True)
@@ -128,6 +132,21 @@ class DeviceContext:
         nm = np.array([int(c.normalize) for c in score], np.int32)
         self._check(self._lib.msh_set_plugins_ex(self.handle, N.ptr(f), len(f), N.ptr(pre), len(pre),
                                                  N.ptr(s), N.ptr(w), N.ptr(nm), len(s)))
+
+    def set_tiebreak(self, mode, seed: int = 0, counter: int = 0) -> None:
+        """msh_set_tiebreak: "first" (the first maximum in List order, the default) or "random" (a
+        uniform choice among the maxima, drawn from SplitMix64(seed) at counter + the pod's position;
+        the counter advances by p per batch call). The integers MSH_TIEBREAK_* pass too."""
+        m = TIEBREAK_MODES.get(mode) if isinstance(mode, (str, int)) and not isinstance(mode, bool) else None
+        if m is None:
+            raise N.MshError(N.MSH_ERR_INVALID, f"tie-break mode {mode!r}: not 'first' (0) or 'random' (1)")
+        self._check(self._lib.msh_set_tiebreak(self.handle, m, int(seed) & _U64, int(counter) & _U64))
+
+    def tiebreak(self) -> tuple[int, int, int]:
+        """msh_get_tiebreak: (mode, seed, counter), the counter where the next batch's first pod draws."""
+        m, s, c = C.c_int32(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.msh_get_tiebreak(self.handle, C.byref(m), C.byref(s), C.byref(c)))
+        return m.value, s.value, c.value
 
     def upload_nodes(self, unsched: np.ndarray, digit: np.ndarray) -> None:
         unsched = np.ascontiguousarray(unsched, np.uint8)
@@ -420,19 +439,25 @@ class Scheduler:
 
     Defaults are the reference's hardcoded plugin lists (initialize.go:80-123):
     filter=[NodeUnschedulable], preScore=[NodeNumber], score=[NodeNumber] (weight 1,
-    no NormalizeScore: nodenumber.go:98-100).
+    no NormalizeScore: nodenumber.go:98-100). tie_break="random" (with tie_seed) picks uniformly
+    among the maximum-score nodes like the reference's selectHost; the default "first" takes the
+    first maximum in List order.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
                  pre_score_plugins: Sequence[str] = (NODE_NUMBER,),
                  score_plugins: Sequence[ScorePluginConfig | str] = (NODE_NUMBER,),
-                 device: int = 0, ctx: DeviceContext | None = None):
+                 device: int = 0, ctx: DeviceContext | None = None, *, tie_break="first", tie_seed: int = 0):
         self.filter_plugins = list(filter_plugins)
         self.pre_score_plugins = list(pre_score_plugins)
         self.score_plugins = [c if isinstance(c, ScorePluginConfig) else ScorePluginConfig(c)
                               for c in score_plugins]
         self.ctx = ctx or DeviceContext(device)
         self.ctx.set_plugins(self.filter_plugins, self.pre_score_plugins, self.score_plugins)
+        # selectHost's tie-break (minisched.go:304-325): "first" keeps the first maximum; "random" spreads
+        # ties uniformly as the reference does (schedule_sequential then raises MSH_ERR_UNSUPPORTED)
+        if tie_break not in ("first", N.MSH_TIEBREAK_FIRST) or tie_seed:
+            self.ctx.set_tiebreak(tie_break, tie_seed)
         self.nodes: NodeTable | None = None
 
     def close(self) -> None:
