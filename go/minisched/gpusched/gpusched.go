@@ -540,6 +540,65 @@ func (x *Ctx) ScheduleSequential(pods []*v1.Pod, b *HostBatch, maxPodsPerNode in
 	return x.results(b), nil
 }
 
+// ---- per-node pod capacity for ScheduleSequential (status.allocatable.pods) ----
+//
+// caps holds one value per uploaded node in List order (the order UploadNodes returned), 0 <= cap <=
+// math.MaxInt32 (in effect unlimited). With a column ScheduleSequential stops at min(cap[i], maxPodsPerNode)
+// per node, or at cap[i] alone when maxPodsPerNode is 0. UploadNodes drops the column; UpdateNodes keeps it;
+// ScheduleBatch ignores it. Like the rest of this package these calls have not been compiled (go/README.md).
+
+// UploadNodeCapacity sets the capacity column.
+func (x *Ctx) UploadNodeCapacity(caps []int32) error {
+	c := make([]C.int32_t, len(caps))
+	for i, v := range caps {
+		c[i] = C.int32_t(v)
+	}
+	if rc := C.msh_upload_node_capacity(x.c, C.int32_t(len(c)), ptrI32(c)); rc != C.MSH_OK {
+		return x.lastErr("msh_upload_node_capacity", rc)
+	}
+	return nil
+}
+
+// PatchNodeCapacity replaces the capacities of the nodes at idx (distinct List-order indices); nothing is rebuilt.
+func (x *Ctx) PatchNodeCapacity(idx, caps []int32) error {
+	if len(idx) != len(caps) {
+		return errors.New("gpusched: idx / caps length mismatch")
+	}
+	ci, cc := make([]C.int32_t, len(idx)), make([]C.int32_t, len(caps))
+	for k := range idx {
+		ci[k], cc[k] = C.int32_t(idx[k]), C.int32_t(caps[k])
+	}
+	if rc := C.msh_patch_node_capacity(x.c, C.int32_t(len(ci)), ptrI32(ci), ptrI32(cc)); rc != C.MSH_OK {
+		return x.lastErr("msh_patch_node_capacity", rc)
+	}
+	return nil
+}
+
+// ClearNodeCapacity goes back to "no column".
+func (x *Ctx) ClearNodeCapacity() error {
+	if rc := C.msh_clear_node_capacity(x.c); rc != C.MSH_OK {
+		return x.lastErr("msh_clear_node_capacity", rc)
+	}
+	return nil
+}
+
+// NodeCapacity returns the column (n entries, the uploaded node count), or nil when none is present.
+func (x *Ctx) NodeCapacity(n int) ([]int32, error) {
+	var present C.int32_t
+	c := make([]C.int32_t, n)
+	if rc := C.msh_node_capacity(x.c, ptrI32(c), &present); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_node_capacity", rc)
+	}
+	if present == 0 {
+		return nil, nil
+	}
+	out := make([]int32, n)
+	for i, v := range c {
+		out[i] = int32(v)
+	}
+	return out, nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

@@ -311,6 +311,40 @@ int msh_schedule_sequential_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_
 int msh_node_pod_counts(msh_ctx* ctx, int32_t* out_counts);
 int msh_reset_node_pod_counts(msh_ctx* ctx);
 
+/* Per-node pod capacity for sequential-commit mode (a node's status.allocatable.pods; additive in ABI 8).
+ * The column. A ctx may hold a capacity column cap[i], one int32 per uploaded node, in List order,
+ *   0 <= cap[i] <= INT32_MAX. Node i is infeasible for every pod while count[i] >= cap[i], where count[i]
+ *   is the assigned-pod count sequential mode already keeps. cap[i] = 0 means the node never takes a pod.
+ *   INT32_MAX is in effect unlimited; there is no sentinel.
+ * Effective capacity. With a column present, msh_schedule_sequential and msh_schedule_sequential_device
+ *   use eff[i] = cap[i] when max_pods_per_node == 0, and eff[i] = min(cap[i], max_pods_per_node) when it
+ *   is positive. They always run the in-order capacity form: one workgroup walks the whole batch, exactly
+ *   as a positive max_pods_per_node does. Statuses, scores and the first-maximum tie-break are those of
+ *   the existing capacity mode: a pod whose class has no available node is MSH_FIT_ERROR, and a pod that
+ *   ends in MSH_SCORE_ERROR commits nothing.
+ * No column. Without a column every call behaves exactly as before, kernel instance included.
+ * Lifetime. msh_upload_nodes drops the column, as it drops score columns, because its nodes are gone.
+ *   msh_patch_nodes and msh_reset_node_pod_counts keep it. Counts carry over from call to call. A patch
+ *   that lowers cap[i] to or below count[i] makes the node full for the next call; raising it makes the
+ *   node available again.
+ * Batch entry points ignore the column: they make no commit.
+ * Limits. The table limit of the capacity form, 262,144 nodes, applies as soon as a column is present
+ *   (larger tables: MSH_ERR_UNSUPPORTED). MSH_TIEBREAK_RANDOM and score-column lists stay refused in
+ *   sequential mode.
+ * Both writers are synchronous and ordered after the ctx's sequential launches in flight; neither rebuilds
+ * the node table.
+ * msh_upload_node_capacity: n != the uploaded node count, or a negative entry: MSH_ERR_INVALID; before
+ *   msh_upload_nodes: MSH_ERR_STATE.
+ * msh_patch_node_capacity: cap[k] replaces the capacity of node idx[k]; idx in [0, n), pairwise distinct
+ *   (MSH_ERR_INVALID otherwise, as a negative entry); no column: MSH_ERR_STATE.
+ * msh_clear_node_capacity: back to "no column".
+ * msh_node_capacity: *out_present = 1 and the n capacities in out_cap (may be NULL) with a column, else
+ *   *out_present = 0 and out_cap untouched. */
+int msh_upload_node_capacity(msh_ctx* ctx, int32_t n, const int32_t* cap);
+int msh_patch_node_capacity(msh_ctx* ctx, int32_t count, const int32_t* idx, const int32_t* cap);
+int msh_clear_node_capacity(msh_ctx* ctx);
+int msh_node_capacity(const msh_ctx* ctx, int32_t* out_cap, int32_t* out_present);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

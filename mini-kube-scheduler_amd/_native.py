@@ -47,6 +47,8 @@ MSH_NORMALIZE_DEFAULT = 1
 MSH_NORMALIZE_DEFAULT_REVERSE = 2
 MSH_NORMALIZE_MINMAX = 3
 
+INT32_MAX = 2**31 - 1  # a node capacity that is in effect unlimited (msh_upload_node_capacity)
+
 MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
 MSH_TIEBREAK_RANDOM = 1  # seeded uniform choice among the maxima (msh_set_tiebreak)
 
@@ -59,6 +61,7 @@ EXPORTED = (
     "msh_schedule_batch", "msh_schedule_batch_async", "msh_wait", "msh_schedule_batch_device",
     "msh_schedule_batches_device", "msh_schedule_sequential",
     "msh_schedule_sequential_device", "msh_node_pod_counts", "msh_reset_node_pod_counts",
+    "msh_upload_node_capacity", "msh_patch_node_capacity", "msh_clear_node_capacity", "msh_node_capacity",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -163,6 +166,10 @@ _SIGS = {
     "msh_schedule_sequential_device": (C.c_int, [_P, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     "msh_node_pod_counts": (C.c_int, [_P, _P]),
     "msh_reset_node_pod_counts": (C.c_int, [_P]),
+    "msh_upload_node_capacity": (C.c_int, [_P, _I32, _P]),
+    "msh_patch_node_capacity": (C.c_int, [_P, _I32, _P, _P]),
+    "msh_clear_node_capacity": (C.c_int, [_P]),
+    "msh_node_capacity": (C.c_int, [_P, _P, C.POINTER(_I32)]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

@@ -404,6 +404,10 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
     c->counts_dirty = false;
   }
   MSH_HIP(c, hipStreamSynchronize(ps));
+  if (up) {  // the capacity column belonged to the previous table's nodes
+    c->have_cap = false;
+    c->h_cap.clear();
+  }
   c->cur = s;
   c->n_nodes = n;
   c->n_pad = n_pad;
@@ -787,6 +791,7 @@ void msh_destroy(msh_ctx* c) {
   }
   c->seq_inflight.clear();  // aliases of the readers' events (destroyed above)
   (void)hipFree(c->d_counts);
+  (void)hipFree(c->d_cap);
   for (hipEvent_t e : c->async_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->tev) {
@@ -1140,7 +1145,11 @@ int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_di
   a.pod_tol = d_pod_tol;
   a.n_pods = p;
   a.pp = c->pp;
-  a.max_pods = max_pods_per_node;
+  // a capacity column: the in-order capacity form with min(cap[i], max_pods_per_node) per node (no scalar:
+  // the column alone)
+  const bool node_cap = c->have_cap;
+  a.max_pods = node_cap && max_pods_per_node == 0 ? INT32_MAX : max_pods_per_node;
+  a.cap = node_cap ? c->d_cap : nullptr;
   a.counts = c->d_counts;
   a.count_stride = (int64_t)c->counts_cap;
   a.count_replicas = c->counts_replicas;
@@ -1148,7 +1157,7 @@ int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_di
   // score): the default runs the per-pair batch kernel with the commit epilogue (pair_kernel<CNT>, every
   // placed pod's count added to a replica), whose placements are msh_schedule_batch's; seq_split = 2 keeps
   // the sequential kernel's 64-pod blocks, = 1 one workgroup walking the batch in order
-  const bool pair_form = max_pods_per_node == 0 && c->dev.seq_split == 2 && p > msh::WAVE &&
+  const bool pair_form = !node_cap && max_pods_per_node == 0 && c->dev.seq_split == 2 && p > msh::WAVE &&
                          c->counts_replicas == msh::SEQ_COUNT_REPLICAS;
   const bool split = pair_form || msh::seq_blocks(a, c->dev) > 1;
   a.fold = !split && c->counts_dirty ? 1 : 0;
@@ -1240,6 +1249,104 @@ int msh_reset_node_pod_counts(msh_ctx* c) {
                             c->prep_stream));
   MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
   c->counts_dirty = false;
+  return MSH_OK;
+}
+
+// The capacity column (not versioned, like the counts it is compared with): both writers go through
+// prep_stream behind the sequential launches in flight, which read the column at their start and end, and
+// finish before they return, so a later launch on any stream sees the new values.
+namespace {
+int cap_write_begin(msh_ctx* c) {
+  if ((size_t)c->n_pad > c->cap_cap) {
+    wait_events(c->seq_inflight);
+    (void)hipFree(c->d_cap);
+    c->d_cap = nullptr;
+    c->cap_cap = 0;
+    MSH_HIP(c, hipMalloc(&c->d_cap, (size_t)c->n_pad * sizeof(int32_t)));
+    c->cap_cap = (size_t)c->n_pad;
+  }
+  return after_seq(c);
+}
+
+// the whole column from c->h_cap (the padding slots 0: they never hold a node)
+int cap_write_all(msh_ctx* c) {
+  const size_t bytes = (size_t)c->n_nodes * sizeof(int32_t);
+  MSH_HIP(c, hipMemsetAsync(c->d_cap, 0, c->cap_cap * sizeof(int32_t), c->prep_stream));
+  if (bytes > 0) {
+    int rc = node_stage(c, bytes);
+    if (rc != MSH_OK) return rc;
+    std::memcpy(c->h_nstage, c->h_cap.data(), bytes);
+    MSH_HIP(c, hipMemcpyAsync(c->d_cap, c->h_nstage, bytes, hipMemcpyHostToDevice, c->prep_stream));
+  }
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+}  // namespace
+
+int msh_upload_node_capacity(msh_ctx* c, int32_t n, const int32_t* cap) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (n != c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "capacity column of " + std::to_string(n) + " entries for " +
+                                        std::to_string(c->n_nodes) + " uploaded nodes");
+  if (n > 0 && !cap) return fail(c, MSH_ERR_INVALID, "null capacity array");
+  for (int32_t i = 0; i < n; ++i)
+    if (cap[i] < 0) return fail(c, MSH_ERR_INVALID, "negative capacity at node " + std::to_string(i));
+  DeviceGuard g(c->device);
+  int rc = cap_write_begin(c);
+  if (rc != MSH_OK) return rc;
+  c->have_cap = false;  // a failed copy leaves no column
+  c->h_cap.assign(cap, cap + n);
+  if ((rc = cap_write_all(c)) != MSH_OK) return rc;
+  c->have_cap = true;
+  return MSH_OK;
+}
+
+int msh_patch_node_capacity(msh_ctx* c, int32_t count, const int32_t* idx, const int32_t* cap) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (!c->have_cap) return fail(c, MSH_ERR_STATE, "msh_upload_node_capacity has not been called");
+  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
+  if (count == 0) return MSH_OK;
+  if (!idx || !cap) return fail(c, MSH_ERR_INVALID, "null patch arrays");
+  std::vector<int32_t> sorted(idx, idx + count);
+  std::sort(sorted.begin(), sorted.end());
+  if (sorted.front() < 0 || sorted.back() >= c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "patch index outside [0, n)");
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return fail(c, MSH_ERR_INVALID, "duplicate patch index");
+  for (int32_t k = 0; k < count; ++k)
+    if (cap[k] < 0) return fail(c, MSH_ERR_INVALID, "negative capacity at patch entry " + std::to_string(k));
+  DeviceGuard g(c->device);
+  int rc = cap_write_begin(c);
+  if (rc != MSH_OK) return rc;
+  for (int32_t k = 0; k < count; ++k) c->h_cap[(size_t)idx[k]] = cap[k];
+  // a few entries: one 4-byte copy each from the page-locked stage; more: the column again
+  constexpr int32_t CAP_PATCH_COPIES = 16;
+  if (count > CAP_PATCH_COPIES) return cap_write_all(c);
+  if ((rc = node_stage(c, (size_t)count * sizeof(int32_t))) != MSH_OK) return rc;
+  std::memcpy(c->h_nstage, cap, (size_t)count * sizeof(int32_t));
+  for (int32_t k = 0; k < count; ++k)
+    MSH_HIP(c, hipMemcpyAsync(c->d_cap + idx[k], c->h_nstage + (size_t)k * sizeof(int32_t), sizeof(int32_t),
+                              hipMemcpyHostToDevice, c->prep_stream));
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+
+int msh_clear_node_capacity(msh_ctx* c) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  c->have_cap = false;  // launches in flight keep reading the device column, which stays allocated
+  c->h_cap.clear();
+  return MSH_OK;
+}
+
+int msh_node_capacity(const msh_ctx* c, int32_t* out_cap, int32_t* out_present) {
+  if (!c || !out_present) return MSH_ERR_INVALID;
+  *out_present = c->have_cap ? 1 : 0;
+  if (c->have_cap && out_cap) std::copy(c->h_cap.begin(), c->h_cap.end(), out_cap);
   return MSH_OK;
 }
 

@@ -76,6 +76,12 @@ struct msh_ctx {
   size_t counts_cap = 0;
   int32_t counts_replicas = 1;
   bool counts_dirty = false;
+  // the capacity column (msh_upload_node_capacity): cap_cap int32 on the device (the padding slots 0) and
+  // its host copy (n_nodes entries, what msh_node_capacity returns); dropped by msh_upload_nodes
+  int32_t* d_cap = nullptr;
+  size_t cap_cap = 0;
+  bool have_cap = false;
+  std::vector<int32_t> h_cap;
   // per caller stream, the event of its last sequential launch: an alias of a table version's reader
   // event (not owned here; track_launch)
   std::vector<std::pair<hipStream_t, hipEvent_t>> seq_inflight;

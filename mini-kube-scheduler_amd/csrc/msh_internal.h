@@ -251,6 +251,10 @@ struct SeqArgs {
   int64_t* out_score;
   int32_t* out_status;
   int32_t pods_per_block;    // set by the launcher: pods per workgroup (the whole batch when one workgroup)
+  // per-node capacities (msh_upload_node_capacity), n_words * 32 entries with the padding slots 0, or null:
+  // node i takes pods while its count is below min(cap[i], max_pods); max_pods is INT32_MAX when the call
+  // gives no scalar capacity. Wave-uniform: the launchers pick the per-node kernel instances by it.
+  const int32_t* cap;
 };
 
 // No-capacity sequential launches (pair_kernel's commit epilogue, seq_kernel's pod blocks) add their

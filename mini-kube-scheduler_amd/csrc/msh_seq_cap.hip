@@ -21,8 +21,12 @@ namespace msh {
 // commits; the identity-like decode (status, score) is done by the lanes once per 64 pods from the
 // scan's first match and the class fallback kept in each pod's lane.
 // ---------------------------------------------------------------------------------------
-template <int RS, bool KX, int U>
-__global__ __launch_bounds__(64) void seq_capu_kernel(SeqArgs a) {
+// PN: per-node capacities (SeqArgs::cap). As in seq_body, lcnt[i] then holds count[i] - min(cap[i], max_pods)
+// for the launch (the negated remaining capacity): full at >= 0, a commit adds 1, and the write-back stores the
+// count again; the per-pod chain is the scalar capacity's with max_pods = 0. cap is read in the prologue and
+// the epilogue only.
+template <int RS, bool KX, int U, bool PN>
+__device__ __forceinline__ void seq_capu_body(SeqArgs a) {
   static_assert(WAVE % U == 0, "a step never straddles a 64-pod block");
   constexpr uint32_t NONE = 0xFFFFFFFFu;
   // [n_words * 32 + 1] pods per node: carried in, updated, written back; the extra slot is the read target
@@ -38,11 +42,11 @@ __global__ __launch_bounds__(64) void seq_capu_kernel(SeqArgs a) {
         a.counts[k * a.count_stride + i] = 0;
       }
     }
-    lcnt[i] = c;
+    lcnt[i] = PN ? c - min(a.cap[i], a.max_pods) : c;
   }
   if (lane == 0) lcnt[slots] = 0;
   __syncthreads();
-  int32_t max_pods = a.max_pods;
+  int32_t max_pods = PN ? 0 : a.max_pods;  // PN: the slots hold count - eff, full at 0
   asm volatile("" : "+s"(max_pods));
   const uint32_t lane_base = (uint32_t)(lane * RS) << 5;  // node index of bit 0 of slot 0's word
   uint32_t D0[RS], D1[RS], D2[RS], D3[RS], AV0[RS], AV1[RS];
@@ -263,7 +267,18 @@ __global__ __launch_bounds__(64) void seq_capu_kernel(SeqArgs a) {
     store_block(j0, a.n_pods - j0);
   }
   __syncthreads();  // every count update has landed
-  for (int32_t i = lane; i < slots; i += WAVE) a.counts[i] = lcnt[i];
+  for (int32_t i = lane; i < slots; i += WAVE) a.counts[i] = PN ? lcnt[i] + min(a.cap[i], a.max_pods) : lcnt[i];
+}
+
+template <int RS, bool KX, int U>
+__global__ __launch_bounds__(64) void seq_capu_kernel(SeqArgs a) {
+  seq_capu_body<RS, KX, U, false>(a);
+}
+
+// Per-node capacities: an instance of its own, so that the scalar capacity's instances are the code they were.
+template <int RS, bool KX, int U>
+__global__ __launch_bounds__(64) void seq_capn_kernel(SeqArgs a) {
+  seq_capu_body<RS, KX, U, true>(a);
 }
 
 namespace {
@@ -272,8 +287,8 @@ constexpr int SEQ_CAP_AHEAD = 4;  // pods per step of seq_capu_kernel
 template <int RS>
 hipError_t launch_capu_rs(const SeqArgs& a, hipStream_t s) {
   const size_t lds = ((size_t)a.n_words * 32 + 1) * sizeof(int32_t);  // <= 128 KB + 4 B (32,768 nodes)
-  auto kx = seq_capu_kernel<RS, true, SEQ_CAP_AHEAD>;
-  auto id = seq_capu_kernel<RS, false, SEQ_CAP_AHEAD>;
+  auto kx = a.cap ? seq_capn_kernel<RS, true, SEQ_CAP_AHEAD> : seq_capu_kernel<RS, true, SEQ_CAP_AHEAD>;
+  auto id = a.cap ? seq_capn_kernel<RS, false, SEQ_CAP_AHEAD> : seq_capu_kernel<RS, false, SEQ_CAP_AHEAD>;
   if (lds > 64 * 1024) {
     const void* k = needs_kx(a.pp) ? reinterpret_cast<const void*>(kx) : reinterpret_cast<const void*>(id);
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

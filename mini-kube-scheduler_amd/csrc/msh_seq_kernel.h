@@ -130,8 +130,15 @@ constexpr int seq_threads(int nw, bool cap, int pw) { return (pw > 1 ? pw : nw +
 // PW: pod waves per workgroup (one scanning wave, pod blocks): each wave holds the whole table and walks
 // 64 / PW consecutive pods of the workgroup's 64-pod block in order; the waves share the block's LDS
 // counts. PW = 1: one wave walks the whole block.
-template <int RS, int NW, bool KX, bool CAP, int U, int PW = 1>
-__global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a0) {
+// PN (with CAP): per-node capacities (SeqArgs::cap, msh_upload_node_capacity). For the launch the slot that
+// holds node i's count holds d[i] = count[i] - eff[i] instead, eff[i] = min(cap[i], max_pods): the negated
+// remaining capacity. The node is full when d[i] >= 0, a commit adds 1 and has filled the node when the new
+// value is >= 0, and the write-back stores count[i] = d[i] + eff[i]. So the per-pod chain is the scalar
+// capacity's with max_pods = 0, instruction for instruction; cap is read in the prologue and the epilogue
+// only (coalesced). Every value fits int32 (0 <= eff, 0 <= count).
+template <int RS, int NW, bool KX, bool CAP, int U, int PW, bool PN>
+__device__ __forceinline__ void seq_body(SeqArgs a0) {
+  static_assert(!PN || CAP, "per-node capacities are a capacity form");
   static_assert(U == 1 || !CAP, "pods are decided ahead of commits only when no commit feeds a decision");
   static_assert(PW == 1 || (NW == 1 && !CAP), "pod waves: one scanning wave, no capacity");
   constexpr bool FIN = !CAP && NW > 1;  // a finalizer wave decodes, keeps the outputs and commits
@@ -202,7 +209,8 @@ __global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a
       VV[r] = g[PLANE_V * PLANE_GW];
       if (CAP) {  // counts carried over from earlier calls: nodes already full
         for (int b = 0; b < 32; ++b)
-          FULL[r] |= (a.counts[w * 32 + b] >= a.max_pods ? 1u : 0u) << b;
+          if constexpr (PN) FULL[r] |= (a.counts[w * 32 + b] >= min(a.cap[w * 32 + b], a.max_pods) ? 1u : 0u) << b;
+          else FULL[r] |= (a.counts[w * 32 + b] >= a.max_pods ? 1u : 0u) << b;
       }
     }
   }
@@ -210,6 +218,9 @@ __global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a
     if (split) {
       for (int32_t i = threadIdx.x; i < a.n_words * 8; i += blockDim.x)
         reinterpret_cast<int4*>(lcnt)[i] = make_int4(0, 0, 0, 0);
+    } else if constexpr (PN) {
+      for (int32_t i = threadIdx.x; i < a.n_words * 32; i += blockDim.x)
+        lcnt[i] = a.counts[i] - min(a.cap[i], a.max_pods);
     } else {
       for (int32_t i = threadIdx.x; i < a.n_words * 32; i += blockDim.x) lcnt[i] = a.counts[i];
     }
@@ -236,6 +247,13 @@ __global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a
     }
   }
   __syncthreads();
+  if constexpr (PN && !LDSC) {
+    // counts in device memory: every FULL plane has been read (the barrier above), so the counts turn into
+    // count - eff in place, ahead of the first commit's atomic
+    for (int32_t i = threadIdx.x; i < a.n_words * 32; i += blockDim.x)
+      a.counts[i] = a.counts[i] - min(a.cap[i], a.max_pods);
+    __syncthreads();
+  }
   int sl = 0;
   // Drain the node-state loads here: otherwise the waitcnt pass, unsure they have landed on every
   // path, waits for every outstanding load (the pod prefetch included) inside the loop.
@@ -437,7 +455,7 @@ __global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a
           if ((int)(q / WAVE) == wv) {  // the owning wave
             int32_t old = 0;
             if (lane == 0) old = LDSC ? atomicAdd(&lcnt[sel], 1) : atomicAdd(&counts[sel], 1);
-            const bool full = __builtin_amdgcn_readfirstlane(old) + 1 >= max_pods;
+            const bool full = __builtin_amdgcn_readfirstlane(old) + 1 >= (PN ? 0 : max_pods);
             if (full) {
               // the owning lane: the register by a wave-uniform index (scalar branches), the lane
               // by a compare
@@ -477,7 +495,19 @@ __global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a
   }
   if (LDSC && !split) {
     __syncthreads();
-    for (int32_t i = threadIdx.x; i < a.n_words * 32; i += blockDim.x) a.counts[i] = lcnt[i];
+    if constexpr (PN) {
+      for (int32_t i = threadIdx.x; i < a.n_words * 32; i += blockDim.x)
+        a.counts[i] = lcnt[i] + min(a.cap[i], a.max_pods);
+    } else {
+      for (int32_t i = threadIdx.x; i < a.n_words * 32; i += blockDim.x) a.counts[i] = lcnt[i];
+    }
+  }
+  if constexpr (PN && !LDSC) {
+    // back to counts. Every commit's atomic has returned to its wave (the wave read its result); they ran at
+    // the device's L2, so the values are read there too, past this CU's vector cache
+    __syncthreads();
+    for (int32_t i = threadIdx.x; i < a.n_words * 32; i += blockDim.x)
+      a.counts[i] = __hip_atomic_load(&a.counts[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + min(a.cap[i], a.max_pods);
   }
   if (PW > 1 && split) {  // the block's counts (every wave's commits) to its device count replica
     __syncthreads();
@@ -489,8 +519,36 @@ __global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a
   }
 }
 
+template <int RS, int NW, bool KX, bool CAP, int U, int PW = 1>
+__global__ __launch_bounds__(seq_threads(NW, CAP, PW)) void seq_kernel(SeqArgs a0) {
+  seq_body<RS, NW, KX, CAP, U, PW, false>(a0);
+}
+
+// The capacity form with per-node capacities (SeqArgs::cap): an instance of its own, so that the scalar
+// capacity's instances are the code they were.
+template <int RS, int NW, bool KX>
+__global__ __launch_bounds__(seq_threads(NW, true, 1)) void seq_node_kernel(SeqArgs a0) {
+  seq_body<RS, NW, KX, true, 1, 1, true>(a0);
+}
+
 namespace seqlaunch {
 constexpr int SEQ_AHEAD = 4;  // pods decided per step without a capacity
+
+// The per-node capacity instances (one workgroup; lds: launch_seq_rs's count table)
+template <int RS, int NW>
+hipError_t launch_seq_node_rs(const SeqArgs& a, size_t lds, hipStream_t s) {
+  const dim3 blk(seq_threads(NW, true, 1));
+  auto kx = seq_node_kernel<RS, NW, true>;
+  auto id = seq_node_kernel<RS, NW, false>;
+  if (lds > 64 * 1024) {
+    const void* k = needs_kx(a.pp) ? reinterpret_cast<const void*>(kx) : reinterpret_cast<const void*>(id);
+    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  if (needs_kx(a.pp)) MSH_TIMED_LAUNCH(kx, dim3(1), blk, lds, s, a);
+  else MSH_TIMED_LAUNCH(id, dim3(1), blk, lds, s, a);
+  return hipGetLastError();
+}
 
 // PW: pod waves per workgroup (one scanning wave, pod blocks), else 1
 template <int RS, int NW, bool CAP, int PW>
@@ -498,6 +556,9 @@ hipError_t launch_seq_rs(const SeqArgs& a, int32_t blocks, hipStream_t s) {
   const dim3 blk(seq_threads(NW, CAP, PW));  // + the finalizer wave without a capacity
   const size_t lds = NW <= 4 ? (size_t)a.n_words * 32 * sizeof(int32_t) : 0;  // seq_kernel's LDSC
   constexpr int U = !CAP ? SEQ_AHEAD : 1;
+  if constexpr (CAP) {
+    if (a.cap) return launch_seq_node_rs<RS, NW>(a, lds, s);
+  }
   auto kx = seq_kernel<RS, NW, true, CAP, U, PW>;
   auto id = seq_kernel<RS, NW, false, CAP, U, PW>;
   const void* k = needs_kx(a.pp) ? reinterpret_cast<const void*>(kx) : reinterpret_cast<const void*>(id);

@@ -261,6 +261,43 @@ class DeviceContext:
     def reset_node_pod_counts(self) -> None:
         self._check(self._lib.msh_reset_node_pod_counts(self.handle))
 
+    # -- per-node pod capacity for sequential mode (a node's status.allocatable.pods) --
+    @staticmethod
+    def _capacities(cap) -> np.ndarray:
+        a = np.asarray(cap)
+        if a.size and (a.dtype.kind not in "iu" or a.min() < -N.INT32_MAX - 1 or a.max() > N.INT32_MAX):
+            raise ValueError("capacities are integers within int32")
+        return np.ascontiguousarray(a, np.int32)
+
+    def upload_node_capacity(self, cap) -> None:
+        """msh_upload_node_capacity: one int32 per uploaded node, List order, 0 <= cap <= INT32_MAX (0: the
+        node never takes a pod; INT32_MAX: in effect unlimited). With a column the sequential calls stop at
+        min(cap[i], max_pods_per_node) per node (the column alone for max_pods_per_node = 0), always in the
+        in-order capacity form. upload_nodes drops the column; patch_nodes and reset_node_pod_counts keep it;
+        the batch entry points ignore it."""
+        cap = self._capacities(cap)
+        self._check(self._lib.msh_upload_node_capacity(self.handle, len(cap), N.ptr(cap)))
+
+    def patch_node_capacity(self, idx, cap) -> None:
+        """msh_patch_node_capacity: cap[k] replaces node idx[k]'s capacity (distinct indices within the table;
+        a column must be present). No table rebuild."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        cap = self._capacities(cap)
+        if len(idx) != len(cap):
+            raise ValueError("idx / cap length mismatch")
+        self._check(self._lib.msh_patch_node_capacity(self.handle, len(idx), N.ptr(idx), N.ptr(cap)))
+
+    def clear_node_capacity(self) -> None:
+        """msh_clear_node_capacity: back to "no column"."""
+        self._check(self._lib.msh_clear_node_capacity(self.handle))
+
+    def node_capacity(self) -> np.ndarray | None:
+        """msh_node_capacity: the column (int32, List order), or None when no column is present."""
+        present = C.c_int32(0)
+        out = np.zeros(self.n_nodes, np.int32)
+        self._check(self._lib.msh_node_capacity(self.handle, N.ptr(out) if self.n_nodes else None, C.byref(present)))
+        return out if present.value else None
+
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):
     # ctypes argument conversion cost ~0.9 us per call next to a ~2.6 us launch.
@@ -442,6 +479,11 @@ class Scheduler:
     no NormalizeScore: nodenumber.go:98-100). tie_break="random" (with tie_seed) picks uniformly
     among the maximum-score nodes like the reference's selectHost; the default "first" takes the
     first maximum in List order.
+
+    Nodes may carry an allocatable-pods value: the attribute `allocatable_pods`, or
+    status.allocatable.pods of a k8s-shaped dict (snapshot.node_allocatable_pods). When any node of the
+    snapshot carries one, schedule_sequential uploads the capacity column (None: INT32_MAX, in effect
+    unlimited) and every node stops at its own limit; schedule_batch ignores it.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
@@ -459,6 +501,7 @@ class Scheduler:
         if tie_break not in ("first", N.MSH_TIEBREAK_FIRST) or tie_seed:
             self.ctx.set_tiebreak(tie_break, tie_seed)
         self.nodes: NodeTable | None = None
+        self._cap_synced = False  # the snapshot's capacity column is on the device
 
     def close(self) -> None:
         self.ctx.close()
@@ -466,7 +509,8 @@ class Scheduler:
     # Replaces the per-cycle Nodes().List (minisched.go:40) with one device upload.
     def update_nodes(self, nodes: Iterable[Any]) -> NodeTable:
         self.nodes = pack_nodes(nodes)
-        self.ctx.upload_nodes(self.nodes.unsched, self.nodes.digit)
+        self.ctx.upload_nodes(self.nodes.unsched, self.nodes.digit)  # drops the device's capacity column
+        self._cap_synced = False
         return self.nodes
 
     def _results(self, pods: PodTable, idx, score, status) -> list[ScheduleResult]:
@@ -506,5 +550,8 @@ class Scheduler:
         if self.nodes is None:
             raise N.MshError(N.MSH_ERR_STATE, "no node snapshot: call update_nodes() first")
         table = pack_pods(pods)
+        if self.nodes.allocatable_pods is not None and not self._cap_synced:
+            self.ctx.upload_node_capacity(self.nodes.allocatable_pods)
+            self._cap_synced = True
         idx, score, status = self.ctx.schedule_sequential(table.digit, table.tolerates, max_pods_per_node)
         return self._results(table, idx, score, status)

@@ -42,6 +42,18 @@ def node_unschedulable(n: Any) -> bool:
     return bool(_get(n, "spec", "unschedulable", default=False))
 
 
+def node_allocatable_pods(n: Any) -> int | None:
+    """The node's pod capacity: the attribute `allocatable_pods`, or status.allocatable.pods of a k8s-shaped
+    dict (an int or a decimal string, as the API serves quantities). None: the node carries none."""
+    v = n.allocatable_pods if hasattr(n, "allocatable_pods") else _get(n, "status", "allocatable", "pods")
+    if v is None:
+        return None
+    v = int(v)
+    if not 0 <= v <= N.INT32_MAX:
+        raise ValueError(f"node {node_name(n)!r}: allocatable pods {v} outside [0, INT32_MAX]")
+    return v
+
+
 def pod_name(p: Any) -> str:
     return p.name if hasattr(p, "name") else _get(p, "metadata", "name", default="")
 
@@ -75,6 +87,8 @@ class NodeTable:
     unsched: np.ndarray       # uint8
     digit: np.ndarray         # int8, -1 = suffix not '0'..'9'
     order: np.ndarray         # int32
+    # int32 pod capacities in List order (INT32_MAX for a node that carries none), or None when no node does
+    allocatable_pods: np.ndarray | None = None
 
     def __len__(self) -> int:
         return len(self.names)
@@ -100,7 +114,11 @@ def pack_nodes(nodes: Iterable[Any]) -> NodeTable:
     out_u = np.empty(n, np.uint8)
     out_d = np.empty(n, np.int8)
     N.check(N.lib().msh_pack_nodes(n, blob, N.ptr(off), N.ptr(uns), N.ptr(order), N.ptr(out_u), N.ptr(out_d)))
-    return NodeTable([names[i] for i in order], out_u, out_d, order)
+    caps = [node_allocatable_pods(x) for x in nodes]
+    cap = None
+    if any(c is not None for c in caps):
+        cap = np.array([N.INT32_MAX if c is None else c for c in caps], np.int32)[order]
+    return NodeTable([names[i] for i in order], out_u, out_d, order, cap)
 
 
 def pod_fields(pods: Sequence[Any]) -> tuple[list[str], list[str], list[Sequence[Any]]]:
