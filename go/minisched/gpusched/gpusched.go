@@ -599,6 +599,103 @@ func (x *Ctx) NodeCapacity(n int) ([]int32, error) {
 	return out, nil
 }
 
+// ---- resource requests for sequential mode (NodeResourcesFit: allocatable, used, requests) ----
+//
+// Amounts are int64 in [0, 2^62], resource-major (a[r*n+i]) in List order, in the caller's units (milli-cpu,
+// bytes). ScheduleSequentialFit places a pod only where every amount it asks for fits alloc - used, and adds its
+// requests to used. UploadNodes drops the table; UpdateNodes keeps it; every other call ignores it. Like the rest
+// of this package these calls have not been compiled (go/README.md).
+
+func toI64(v []int64) []C.int64_t {
+	c := make([]C.int64_t, len(v))
+	for i, x := range v {
+		c[i] = C.int64_t(x)
+	}
+	return c
+}
+
+// UploadNodeResources sets the table: alloc (and used, nil = zeros) hold nres*n values.
+func (x *Ctx) UploadNodeResources(n, nres int, alloc, used []int64) error {
+	if len(alloc) != n*nres || (used != nil && len(used) != n*nres) {
+		return errors.New("gpusched: alloc / used hold nres*n values")
+	}
+	if rc := C.msh_upload_node_resources(x.c, C.int32_t(n), C.int32_t(nres), ptrI64(toI64(alloc)), ptrI64(toI64(used))); rc != C.MSH_OK {
+		return x.lastErr("msh_upload_node_resources", rc)
+	}
+	return nil
+}
+
+// PatchNodeResources replaces the values of the nodes at idx (distinct List-order indices): alloc / used hold
+// nres*len(idx) values (a[r*len(idx)+k]), nil keeps that array. Nothing is rebuilt.
+func (x *Ctx) PatchNodeResources(idx []int32, alloc, used []int64) error {
+	ci := make([]C.int32_t, len(idx))
+	for k := range idx {
+		ci[k] = C.int32_t(idx[k])
+	}
+	if rc := C.msh_patch_node_resources(x.c, C.int32_t(len(ci)), ptrI32(ci), ptrI64(toI64(alloc)), ptrI64(toI64(used))); rc != C.MSH_OK {
+		return x.lastErr("msh_patch_node_resources", rc)
+	}
+	return nil
+}
+
+// ClearNodeResources goes back to "no table".
+func (x *Ctx) ClearNodeResources() error {
+	if rc := C.msh_clear_node_resources(x.c); rc != C.MSH_OK {
+		return x.lastErr("msh_clear_node_resources", rc)
+	}
+	return nil
+}
+
+// NodeResources returns nres, alloc and used (nres*n values each, n the uploaded node count), or nres = 0 when no
+// table is present.
+func (x *Ctx) NodeResources(n int) (nres int, alloc, used []int64, err error) {
+	var present, nr C.int32_t
+	a, u := make([]C.int64_t, n*int(C.MSH_MAX_RESOURCES)), make([]C.int64_t, n*int(C.MSH_MAX_RESOURCES))
+	if rc := C.msh_node_resources(x.c, &nr, ptrI64(a), ptrI64(u), &present); rc != C.MSH_OK {
+		return 0, nil, nil, x.lastErr("msh_node_resources", rc)
+	}
+	if present == 0 {
+		return 0, nil, nil, nil
+	}
+	nres = int(nr)
+	alloc, used = make([]int64, nres*n), make([]int64, nres*n)
+	for i := range alloc {
+		alloc[i], used[i] = int64(a[i]), int64(u[i])
+	}
+	return nres, alloc, used, nil
+}
+
+// ScheduleSequentialFit is ScheduleSequential with per-pod requests: req holds nres*len(pods) values
+// (req[r*len(pods)+j]).
+func (x *Ctx) ScheduleSequentialFit(pods []*v1.Pod, b *HostBatch, nres int, req []int64, maxPodsPerNode int32) ([]Result, error) {
+	if !x.hasNodes {
+		return nil, errors.New("gpusched: UploadNodes has not been called")
+	}
+	if len(req) != nres*len(pods) {
+		return nil, errors.New("gpusched: req holds nres*len(pods) values")
+	}
+	if err := x.pack(b, pods); err != nil {
+		return nil, err
+	}
+	p := len(pods)
+	if rc := C.msh_schedule_sequential_fit(x.c, C.int32_t(p), ptrI8(b.pd[:p]), ptrU8(b.pt[:p]), C.int32_t(nres),
+		ptrI64(toI64(req)), C.int32_t(maxPodsPerNode), ptrI32(b.idx[:p]), ptrI64(b.score[:p]), ptrI32(b.status[:p]), nil, nil); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_schedule_sequential_fit", rc)
+	}
+	return x.results(b), nil
+}
+
+// ScheduleSequentialFitDevice is the asynchronous form over device pointers (msh_schedule_sequential_fit_device);
+// dReq is not validated by the library.
+func (x *Ctx) ScheduleSequentialFitDevice(p int, dPodDigit, dPodTol unsafe.Pointer, nres int, dReq unsafe.Pointer,
+	maxPodsPerNode int32, dIdx, dScore, dStatus, stream unsafe.Pointer) error {
+	if rc := C.msh_schedule_sequential_fit_device(x.c, C.int32_t(p), (*C.int8_t)(dPodDigit), (*C.uint8_t)(dPodTol), C.int32_t(nres),
+		(*C.int64_t)(dReq), C.int32_t(maxPodsPerNode), (*C.int32_t)(dIdx), (*C.int64_t)(dScore), (*C.int32_t)(dStatus), stream); rc != C.MSH_OK {
+		return x.lastErr("msh_schedule_sequential_fit_device", rc)
+	}
+	return nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

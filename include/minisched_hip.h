@@ -345,6 +345,62 @@ int msh_patch_node_capacity(msh_ctx* ctx, int32_t count, const int32_t* idx, con
 int msh_clear_node_capacity(msh_ctx* ctx);
 int msh_node_capacity(const msh_ctx* ctx, int32_t* out_cap, int32_t* out_present);
 
+/* Resource requests for sequential-commit mode (upstream's NodeResourcesFit as a build extension, in the same
+ * sense as the pod capacity; additive in ABI 8).
+ * The table. A ctx may hold a resource table of nres resources, 1 <= nres <= MSH_MAX_RESOURCES. Per uploaded
+ *   node i and resource r it holds two int64: alloc[r][i], the node's allocatable amount, and used[r][i], the
+ *   sum of the committed requests (NodeInfo.Requested), both in [0, MSH_RESOURCE_MAX] = [0, 2^62]. Arrays are
+ *   resource-major, a[r * n + i], in List order. Units are the caller's (milli-cpu, bytes, ...).
+ * msh_schedule_sequential_fit / _fit_device: the in-order loop of the capacity form with one more conjunct in
+ *   feasibility. Pods are decided strictly in order; pod j carries requests req[r][j] (pod_req[r * p + j], each
+ *   in [0, 2^62]). Node i is feasible for pod j iff the filter list passes (unchanged), count[i] < eff[i] (eff
+ *   as msh_schedule_sequential uses it, from max_pods_per_node and / or the capacity column; with neither there
+ *   is no count limit), and for every r with req[r][j] > 0: req[r][j] <= alloc[r][i] - used[r][i]. So a zero
+ *   request never rejects, even where a patch has lowered alloc below used, and an exact fit passes. Status,
+ *   score and the first-maximum tie-break over the feasible set are the capacity form's: MSH_FIT_ERROR when no
+ *   node is feasible, otherwise MSH_SCORE_ERROR (which commits nothing), otherwise MSH_PLACED, whose commit
+ *   adds 1 to count[sel] and req[r][j] to used[r][sel] for every r. used and the counts carry over from call to
+ *   call, across a mix of _fit and plain sequential calls too.
+ * The device form is asynchronous, as msh_schedule_sequential_device, and does not validate d_pod_req: values
+ *   outside [0, 2^62] are the caller's error (the host form returns MSH_ERR_INVALID for them).
+ * Refusals: no resource table: MSH_ERR_STATE; nres != the table's: MSH_ERR_INVALID; MSH_TIEBREAK_RANDOM and a
+ *   score-column list: MSH_ERR_UNSUPPORTED, as in sequential mode; a table past the kernel's limit:
+ *   MSH_ERR_UNSUPPORTED. The limit: the node state lives in the registers of one workgroup, 8,192 nodes for a
+ *   table of one or two resources, 4,096 for three or four.
+ * Unchanged calls. msh_schedule_sequential* and every batch entry point ignore the table: their pods request
+ *   nothing and commit nothing to used. With no table every existing call behaves as before, kernel instance
+ *   included.
+ * Lifetime and ordering are the capacity column's: msh_upload_nodes drops the table; msh_patch_nodes and
+ *   msh_reset_node_pod_counts keep it and do not touch used (used changes only through commits, an upload or a
+ *   patch). The writers and the reader are synchronous, ordered after the ctx's sequential launches in flight,
+ *   and do not rebuild the node table. A patch of used is how a caller accounts for a deleted pod, or for pods
+ *   bound before the scheduler started.
+ * msh_upload_node_resources: used NULL = zeros. n != the uploaded node count, nres outside
+ *   1..MSH_MAX_RESOURCES, a value outside [0, 2^62]: MSH_ERR_INVALID; before msh_upload_nodes: MSH_ERR_STATE.
+ * msh_patch_node_resources: alloc[r * count + k] / used[r * count + k] replace node idx[k]'s values (NULL: keep
+ *   that array); idx in [0, n), pairwise distinct, values in range, not both arrays NULL (MSH_ERR_INVALID
+ *   otherwise); no table: MSH_ERR_STATE.
+ * msh_clear_node_resources: back to "no table".
+ * msh_node_resources: *out_present = 1, *out_nres (may be NULL) and the nres * n values in out_alloc / out_used
+ *   (each may be NULL) with a table; else *out_present = 0 and the arrays untouched.
+ * A failed call changes nothing. */
+#define MSH_MAX_RESOURCES 4
+#define MSH_RESOURCE_MAX ((int64_t)1 << 62)
+int msh_upload_node_resources(msh_ctx* ctx, int32_t n, int32_t nres, const int64_t* alloc, const int64_t* used);
+int msh_patch_node_resources(msh_ctx* ctx, int32_t count, const int32_t* idx, const int64_t* alloc,
+                             const int64_t* used);
+int msh_clear_node_resources(msh_ctx* ctx);
+int msh_node_resources(msh_ctx* ctx, int32_t* out_nres, int64_t* out_alloc, int64_t* out_used,
+                       int32_t* out_present);
+int msh_schedule_sequential_fit(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                int32_t nres, const int64_t* pod_req, int32_t max_pods_per_node,
+                                int32_t* out_idx, int64_t* out_score, int32_t* out_status,
+                                msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_fit_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit,
+                                       const uint8_t* d_pod_tol, int32_t nres, const int64_t* d_pod_req,
+                                       int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
+                                       int32_t* d_out_status, void* stream);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

@@ -49,6 +49,9 @@ MSH_NORMALIZE_MINMAX = 3
 
 INT32_MAX = 2**31 - 1  # a node capacity that is in effect unlimited (msh_upload_node_capacity)
 
+MAX_RESOURCES = 4        # MSH_MAX_RESOURCES
+RESOURCE_MAX = 1 << 62   # MSH_RESOURCE_MAX: the largest allocatable / used / requested amount
+
 MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
 MSH_TIEBREAK_RANDOM = 1  # seeded uniform choice among the maxima (msh_set_tiebreak)
 
@@ -62,6 +65,8 @@ EXPORTED = (
     "msh_schedule_batches_device", "msh_schedule_sequential",
     "msh_schedule_sequential_device", "msh_node_pod_counts", "msh_reset_node_pod_counts",
     "msh_upload_node_capacity", "msh_patch_node_capacity", "msh_clear_node_capacity", "msh_node_capacity",
+    "msh_upload_node_resources", "msh_patch_node_resources", "msh_clear_node_resources", "msh_node_resources",
+    "msh_schedule_sequential_fit", "msh_schedule_sequential_fit_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -170,6 +175,12 @@ _SIGS = {
     "msh_patch_node_capacity": (C.c_int, [_P, _I32, _P, _P]),
     "msh_clear_node_capacity": (C.c_int, [_P]),
     "msh_node_capacity": (C.c_int, [_P, _P, C.POINTER(_I32)]),
+    "msh_upload_node_resources": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "msh_patch_node_resources": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "msh_clear_node_resources": (C.c_int, [_P]),
+    "msh_node_resources": (C.c_int, [_P, C.POINTER(_I32), _P, _P, C.POINTER(_I32)]),
+    "msh_schedule_sequential_fit": (C.c_int, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_fit_device": (C.c_int, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

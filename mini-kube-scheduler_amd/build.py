@@ -33,6 +33,7 @@ SOURCES = [
     ("msh_generic.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_cap.hip", "hipcc", ["-x", "hip"]),
+    ("msh_seq_fit.hip", "hipcc", ["-x", "hip"]),
     ("msh_prep.hip", "hipcc", ["-x", "hip"]),
     ("msh_capi.cpp", "hipcc", []),
     ("msh_shard.cpp", "hipcc", []),

@@ -407,6 +407,8 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
   if (up) {  // the capacity column belonged to the previous table's nodes
     c->have_cap = false;
     c->h_cap.clear();
+    c->have_res = false;  // and so did the resource table
+    c->nres = 0;
   }
   c->cur = s;
   c->n_nodes = n;
@@ -792,6 +794,8 @@ void msh_destroy(msh_ctx* c) {
   c->seq_inflight.clear();  // aliases of the readers' events (destroyed above)
   (void)hipFree(c->d_counts);
   (void)hipFree(c->d_cap);
+  (void)hipFree(c->d_alloc);
+  (void)hipFree(c->d_used);
   for (hipEvent_t e : c->async_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->tev) {
@@ -1121,21 +1125,46 @@ int msh_wait(msh_ctx* c, uint64_t ticket) {
   return MSH_OK;
 }
 
-int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
-                                   const uint8_t* d_pod_tol, int32_t max_pods_per_node,
-                                   int32_t* d_out_idx, int64_t* d_out_score,
-                                   int32_t* d_out_status, void* stream) {
+namespace {
+// The pods' resource requests of a msh_schedule_sequential_fit* call (device-visible memory), or none: the
+// plain sequential call.
+struct FitReq {
+  int32_t nres = 0;  // 0: no requests
+  const int64_t* d_pod_req = nullptr;
+};
+
+// What a resource-fit call needs of the ctx, checked before any device work: a resource table of the call's
+// nres, within the kernel's table limit.
+int fit_check(msh_ctx* c, int32_t nres) {
+  if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+  if (nres != c->nres)
+    return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
+                                        std::to_string(c->nres));
+  if (c->n_nodes > msh::seq_fit_max_nodes(nres))
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "the resource-fit form keeps the node state in registers: at most " +
+                    std::to_string(msh::seq_fit_max_nodes(nres)) + " nodes per device with " + std::to_string(nres) +
+                    (nres == 1 ? " resource" : " resources"));
+  return MSH_OK;
+}
+
+// msh_schedule_sequential_device and msh_schedule_sequential_fit_device (`entry`: the name for messages)
+int seq_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+               const FitReq& fit, int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
+               int32_t* d_out_status, void* stream) {
   if (!c) return MSH_ERR_INVALID;
   c->err.clear();
   if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // d_out_score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = refuse_random(c, "msh_schedule_sequential_device");
+  if (fit.nres && p > 0 && !fit.d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
+  int rc = refuse_random(c, entry);
   if (rc != MSH_OK) return rc;
   if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
   DeviceGuard g(c->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if ((rc = ready(c)) != MSH_OK) return rc;
+  if (fit.nres && (rc = fit_check(c, fit.nres)) != MSH_OK) return rc;
   msh::SeqArgs a{};
   const NodeTable& t = cur_table(c);
   a.planes = t.d_planes;
@@ -1157,9 +1186,11 @@ int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_di
   // score): the default runs the per-pair batch kernel with the commit epilogue (pair_kernel<CNT>, every
   // placed pod's count added to a replica), whose placements are msh_schedule_batch's; seq_split = 2 keeps
   // the sequential kernel's 64-pod blocks, = 1 one workgroup walking the batch in order
-  const bool pair_form = !node_cap && max_pods_per_node == 0 && c->dev.seq_split == 2 && p > msh::WAVE &&
-                         c->counts_replicas == msh::SEQ_COUNT_REPLICAS;
-  const bool split = pair_form || msh::seq_blocks(a, c->dev) > 1;
+  // (requests: always one workgroup in order, the pod count unlimited when neither a scalar nor a column limits it)
+  const bool pair_form = !fit.nres && !node_cap && max_pods_per_node == 0 && c->dev.seq_split == 2 &&
+                         p > msh::WAVE && c->counts_replicas == msh::SEQ_COUNT_REPLICAS;
+  const bool split = !fit.nres && (pair_form || msh::seq_blocks(a, c->dev) > 1);
+  if (fit.nres && a.max_pods == 0) a.max_pods = INT32_MAX;
   a.fold = !split && c->counts_dirty ? 1 : 0;
   // one sequential launch of a ctx at a time: each commits into (and a fold rewrites) the same counts,
   // so this stream first waits for the ctx's sequential launches in flight on other streams
@@ -1179,6 +1210,16 @@ int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_di
     pa.count_stride = (int64_t)c->counts_cap;
     TimedLaunch tl(c);
     e = msh::launch_pairs(pa, false, c->dev, s);
+  } else if (fit.nres) {
+    msh::FitArgs f{};
+    f.s = a;
+    f.nres = fit.nres;
+    f.res_stride = (int64_t)c->res_cap;
+    f.alloc = c->d_alloc;
+    f.used = c->d_used;
+    f.pod_req = fit.d_pod_req;
+    TimedLaunch tl(c);
+    e = msh::launch_seq_fit(f, s, &err);
   } else {
     TimedLaunch tl(c);
     e = msh::launch_sequential(a, c->dev, s, &err);
@@ -1191,30 +1232,91 @@ int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_di
   return p > 0 ? track_launch(c, s, true) : MSH_OK;
 }
 
-int msh_schedule_sequential(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                            int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
-                            int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+// msh_schedule_sequential and msh_schedule_sequential_fit (nres = 0: no requests)
+int seq_host(msh_ctx* c, const char* entry, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol, int32_t nres,
+             const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+             int32_t* out_status, msh_commit_cb commit_cb, void* user) {
   if (!c) return MSH_ERR_INVALID;
   c->err.clear();
   if (p < 0) return fail(c, MSH_ERR_INVALID, "negative pod count");
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // out_score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
-  int rc = refuse_random(c, "msh_schedule_sequential");
+  if (nres && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
+  int rc = refuse_random(c, entry);
   if (rc != MSH_OK) return rc;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (nres) {
+    if (max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
+    if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
+    if ((rc = fit_check(c, nres)) != MSH_OK) return rc;
+    for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e)
+      if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
+        return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
+  }
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
   if ((rc = ready(c)) != MSH_OK) return rc;
   HostIO io;
   if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  rc = msh_schedule_sequential_device(c, p, io.d_pd, io.d_pt, max_pods_per_node, io.o_idx, io.o_score,
-                                      io.o_status, c->stream);
+  FitReq fit;
+  if (nres) {
+    // the requests through the page-locked node stage, which the kernel reads itself (free here: every writer
+    // that uses it has finished its copies, and this call ends only when the kernel has)
+    const size_t bytes = (size_t)nres * (size_t)p * sizeof(int64_t);
+    if ((rc = node_stage(c, bytes)) != MSH_OK) return rc;
+    std::memcpy(c->h_nstage, pod_req, bytes);
+    fit.nres = nres;
+    fit.d_pod_req = reinterpret_cast<const int64_t*>(c->h_nstage);
+  }
+  rc = seq_device(c, entry, p, io.d_pd, io.d_pt, fit, max_pods_per_node, io.o_idx, io.o_score, io.o_status,
+                  c->stream);
   if (rc != MSH_OK) return rc;
   if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
   if (commit_cb)
     for (int32_t j = 0; j < p; j++)
       if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
   return MSH_OK;
+}
+}  // namespace
+
+int msh_schedule_sequential_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
+                                   const uint8_t* d_pod_tol, int32_t max_pods_per_node,
+                                   int32_t* d_out_idx, int64_t* d_out_score,
+                                   int32_t* d_out_status, void* stream) {
+  return seq_device(c, "msh_schedule_sequential_device", p, d_pod_digit, d_pod_tol, FitReq{}, max_pods_per_node,
+                    d_out_idx, d_out_score, d_out_status, stream);
+}
+
+int msh_schedule_sequential(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                            int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+                            int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  return seq_host(c, "msh_schedule_sequential", p, pod_digit, pod_tol, 0, nullptr, max_pods_per_node, out_idx,
+                  out_score, out_status, commit_cb, user);
+}
+
+int msh_schedule_sequential_fit_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                       int32_t nres, const int64_t* d_pod_req, int32_t max_pods_per_node,
+                                       int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
+                                       void* stream) {
+  if (!c) return MSH_ERR_INVALID;
+  if (nres < 1 || nres > MSH_MAX_RESOURCES) {
+    c->err.clear();
+    return fail(c, MSH_ERR_INVALID, "nres outside [1, MSH_MAX_RESOURCES]");
+  }
+  return seq_device(c, "msh_schedule_sequential_fit_device", p, d_pod_digit, d_pod_tol, FitReq{nres, d_pod_req},
+                    max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+}
+
+int msh_schedule_sequential_fit(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol, int32_t nres,
+                                const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  if (!c) return MSH_ERR_INVALID;
+  if (nres < 1 || nres > MSH_MAX_RESOURCES) {
+    c->err.clear();
+    return fail(c, MSH_ERR_INVALID, "nres outside [1, MSH_MAX_RESOURCES]");
+  }
+  return seq_host(c, "msh_schedule_sequential_fit", p, pod_digit, pod_tol, nres, pod_req, max_pods_per_node, out_idx,
+                  out_score, out_status, commit_cb, user);
 }
 
 int msh_node_pod_counts(msh_ctx* c, int32_t* out_counts) {
@@ -1347,6 +1449,146 @@ int msh_node_capacity(const msh_ctx* c, int32_t* out_cap, int32_t* out_present) 
   if (!c || !out_present) return MSH_ERR_INVALID;
   *out_present = c->have_cap ? 1 : 0;
   if (c->have_cap && out_cap) std::copy(c->h_cap.begin(), c->h_cap.end(), out_cap);
+  return MSH_OK;
+}
+
+// The resource table (not versioned, like the counts and the capacity column): the writers and the reader go
+// through prep_stream behind the sequential launches in flight, which read the table at their start and write
+// `used` at their end, and finish before they return.
+namespace {
+bool res_values_ok(const int64_t* v, size_t len, size_t* bad) {
+  for (size_t e = 0; e < len; ++e)
+    if (v[e] < 0 || v[e] > MSH_RESOURCE_MAX) {
+      *bad = e;
+      return false;
+    }
+  return true;
+}
+}  // namespace
+
+int msh_upload_node_resources(msh_ctx* c, int32_t n, int32_t nres, const int64_t* alloc, const int64_t* used) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (n != c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "resource table of " + std::to_string(n) + " nodes for " +
+                                        std::to_string(c->n_nodes) + " uploaded nodes");
+  if (nres < 1 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [1, MSH_MAX_RESOURCES]");
+  if (n > 0 && !alloc) return fail(c, MSH_ERR_INVALID, "null allocatable array");
+  const size_t len = (size_t)nres * (size_t)n;
+  size_t bad = 0;
+  if (!res_values_ok(alloc, len, &bad))
+    return fail(c, MSH_ERR_INVALID, "allocatable outside [0, 2^62] at node " + std::to_string(bad % (size_t)n));
+  if (used && !res_values_ok(used, len, &bad))
+    return fail(c, MSH_ERR_INVALID, "used outside [0, 2^62] at node " + std::to_string(bad % (size_t)n));
+  DeviceGuard g(c->device);
+  if ((size_t)c->n_pad > c->res_cap || nres > c->res_rows) {
+    const size_t rows = (size_t)nres;
+    wait_events(c->seq_inflight);
+    (void)hipFree(c->d_alloc);
+    (void)hipFree(c->d_used);
+    c->d_alloc = c->d_used = nullptr;
+    c->res_cap = 0;
+    c->res_rows = 0;
+    c->have_res = false;
+    c->nres = 0;
+    MSH_HIP(c, hipMalloc(&c->d_alloc, rows * (size_t)c->n_pad * sizeof(int64_t)));
+    MSH_HIP(c, hipMalloc(&c->d_used, rows * (size_t)c->n_pad * sizeof(int64_t)));
+    c->res_cap = (size_t)c->n_pad;
+    c->res_rows = nres;
+  }
+  int rc = after_seq(c);
+  if (rc != MSH_OK) return rc;
+  c->have_res = false;  // a failed copy leaves no table
+  c->nres = 0;
+  hipStream_t ps = c->prep_stream;
+  const size_t all = (size_t)c->res_rows * c->res_cap * sizeof(int64_t), row = (size_t)n * sizeof(int64_t);
+  MSH_HIP(c, hipMemsetAsync(c->d_alloc, 0, all, ps));  // the padding slots: 0
+  MSH_HIP(c, hipMemsetAsync(c->d_used, 0, all, ps));
+  if (len > 0) {
+    if ((rc = node_stage(c, 2 * len * sizeof(int64_t))) != MSH_OK) return rc;
+    int64_t* st = reinterpret_cast<int64_t*>(c->h_nstage);
+    std::memcpy(st, alloc, len * sizeof(int64_t));
+    if (used) std::memcpy(st + len, used, len * sizeof(int64_t));
+    for (int32_t r = 0; r < nres; ++r) {
+      MSH_HIP(c, hipMemcpyAsync(c->d_alloc + (size_t)r * c->res_cap, st + (size_t)r * n, row, hipMemcpyHostToDevice, ps));
+      if (used)
+        MSH_HIP(c, hipMemcpyAsync(c->d_used + (size_t)r * c->res_cap, st + len + (size_t)r * n, row,
+                                  hipMemcpyHostToDevice, ps));
+    }
+  }
+  MSH_HIP(c, hipStreamSynchronize(ps));
+  c->nres = nres;
+  c->have_res = true;
+  return MSH_OK;
+}
+
+int msh_patch_node_resources(msh_ctx* c, int32_t count, const int32_t* idx, const int64_t* alloc,
+                             const int64_t* used) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
+  if (!alloc && !used) return fail(c, MSH_ERR_INVALID, "a patch of neither allocatable nor used");
+  if (count == 0) return MSH_OK;
+  if (!idx) return fail(c, MSH_ERR_INVALID, "null patch indices");
+  std::vector<int32_t> sorted(idx, idx + count);
+  std::sort(sorted.begin(), sorted.end());
+  if (sorted.front() < 0 || sorted.back() >= c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "patch index outside [0, n)");
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return fail(c, MSH_ERR_INVALID, "duplicate patch index");
+  const size_t len = (size_t)c->nres * (size_t)count;
+  size_t bad = 0;
+  if ((alloc && !res_values_ok(alloc, len, &bad)) || (used && !res_values_ok(used, len, &bad)))
+    return fail(c, MSH_ERR_INVALID, "value outside [0, 2^62] at patch entry " + std::to_string(bad % (size_t)count));
+  DeviceGuard g(c->device);
+  int rc = after_seq(c);
+  if (rc != MSH_OK) return rc;
+  // indices and values through the page-locked stage, scattered by one small kernel that reads it
+  const size_t ibytes = ((size_t)count * sizeof(int32_t) + 7) & ~(size_t)7;
+  if ((rc = node_stage(c, ibytes + 2 * len * sizeof(int64_t))) != MSH_OK) return rc;
+  int32_t* si = reinterpret_cast<int32_t*>(c->h_nstage);
+  int64_t* sa = reinterpret_cast<int64_t*>(c->h_nstage + ibytes);
+  int64_t* su = sa + len;
+  std::memcpy(si, idx, (size_t)count * sizeof(int32_t));
+  if (alloc) std::memcpy(sa, alloc, len * sizeof(int64_t));
+  if (used) std::memcpy(su, used, len * sizeof(int64_t));
+  hipError_t e = msh::launch_res_patch(si, alloc ? sa : nullptr, used ? su : nullptr, count, c->nres,
+                                       (int64_t)c->res_cap, c->d_alloc, c->d_used, c->prep_stream);
+  if (e != hipSuccess) return hip_fail(c, e, "res_patch_kernel");
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+
+int msh_clear_node_resources(msh_ctx* c) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  c->have_res = false;  // launches in flight keep reading the device table, which stays allocated
+  c->nres = 0;
+  return MSH_OK;
+}
+
+int msh_node_resources(msh_ctx* c, int32_t* out_nres, int64_t* out_alloc, int64_t* out_used, int32_t* out_present) {
+  if (!c || !out_present) return MSH_ERR_INVALID;
+  c->err.clear();
+  *out_present = c->have_res ? 1 : 0;
+  if (out_nres) *out_nres = c->have_res ? c->nres : 0;
+  if (!c->have_res || c->n_nodes == 0 || (!out_alloc && !out_used)) return MSH_OK;
+  DeviceGuard g(c->device);
+  int rc = after_seq(c);  // sequential launches of this ctx in flight update `used`
+  if (rc != MSH_OK) return rc;
+  const size_t row = (size_t)c->n_nodes * sizeof(int64_t);
+  for (int32_t r = 0; r < c->nres; ++r) {
+    if (out_alloc)
+      MSH_HIP(c, hipMemcpyAsync(out_alloc + (size_t)r * c->n_nodes, c->d_alloc + (size_t)r * c->res_cap, row,
+                                hipMemcpyDeviceToHost, c->prep_stream));
+    if (out_used)
+      MSH_HIP(c, hipMemcpyAsync(out_used + (size_t)r * c->n_nodes, c->d_used + (size_t)r * c->res_cap, row,
+                                hipMemcpyDeviceToHost, c->prep_stream));
+  }
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
   return MSH_OK;
 }
 

@@ -82,6 +82,15 @@ struct msh_ctx {
   size_t cap_cap = 0;
   bool have_cap = false;
   std::vector<int32_t> h_cap;
+  // the resource table (msh_upload_node_resources): nres rows of res_cap int64 each for alloc and for used
+  // (row r at r * res_cap, the padding slots 0), on the device only: used changes with every commit of
+  // msh_schedule_sequential_fit, so msh_node_resources reads both back; dropped by msh_upload_nodes
+  int64_t* d_alloc = nullptr;
+  int64_t* d_used = nullptr;
+  size_t res_cap = 0;
+  int32_t res_rows = 0;  // rows allocated (>= nres)
+  int32_t nres = 0;
+  bool have_res = false;
   // per caller stream, the event of its last sequential launch: an alias of a table version's reader
   // event (not owned here; track_launch)
   std::vector<std::pair<hipStream_t, hipEvent_t>> seq_inflight;

@@ -273,6 +273,24 @@ hipError_t launch_count_fold(int32_t* counts, int64_t stride, int32_t replicas, 
 hipError_t launch_sequential(const SeqArgs& a, const DeviceInfo& dev, hipStream_t s, std::string* err);
 // The capacity form (msh_seq_cap.hip): nw scanning waves with rs words per lane, one workgroup.
 hipError_t launch_seq_capacity(const SeqArgs& a, int nw, int rs, hipStream_t s);
+// The resource-fit form (msh_seq_fit.hip, msh_schedule_sequential_fit): the capacity form's in-order loop with
+// per-node int64 free amounts. s.max_pods is INT32_MAX when neither a scalar nor a capacity column limits the
+// pod count; s.fold as for the other one-workgroup forms.
+constexpr int FIT_MAX_RES = 4;  // MSH_MAX_RESOURCES
+struct FitArgs {
+  SeqArgs s;
+  int32_t nres;            // 1..FIT_MAX_RES
+  int64_t res_stride;      // entries between two resources' rows of alloc / used (>= s.n_words * 32, padding 0)
+  const int64_t* alloc;    // [nres][res_stride]
+  int64_t* used;           // [nres][res_stride]: read at the start, written back at the end
+  const int64_t* pod_req;  // [nres][s.n_pods]
+};
+// Nodes the resource-fit kernel holds for a table of nres resources (8,192 up to two, 4,096 for three or four).
+int32_t seq_fit_max_nodes(int32_t nres);
+hipError_t launch_seq_fit(const FitArgs& a, hipStream_t s, std::string* err);
+// alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
+hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
+                            int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);
 // Pod waves per pod-block workgroup without a capacity (one scanning wave): each walks 64 / this many pods.
 constexpr int SEQ_POD_WAVES = 1;  // measured: 1 / 2 / 4 / 8 waves 11.6 / 14.2 / 13.2 / 18.3 us per C5 launch (profiles/ab/r6_seq_pod_waves.jsonl)
 int seq_pod_waves(const DeviceInfo& dev);

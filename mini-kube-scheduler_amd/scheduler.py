@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _native as N
 from .framework import (NODE_NUMBER, NODE_UNSCHEDULABLE, SCORE_COLUMNS, Normalize, Outcome, ScheduleResult)
-from .snapshot import NodeTable, PodTable, pack_nodes, pack_pods
+from .snapshot import NodeTable, PodTable, node_allocatable, pack_nodes, pack_pods, pod_requests
 
 FILTER_IDS = {NODE_UNSCHEDULABLE: N.MSH_PLUGIN_NODE_UNSCHEDULABLE}
 SCORE_IDS = {NODE_NUMBER: N.MSH_PLUGIN_NODE_NUMBER,
@@ -298,6 +298,82 @@ class DeviceContext:
         self._check(self._lib.msh_node_capacity(self.handle, N.ptr(out) if self.n_nodes else None, C.byref(present)))
         return out if present.value else None
 
+    # -- resource requests for sequential mode (NodeResourcesFit: allocatable, used, requests) --
+    @staticmethod
+    def _amounts(a, ndim: int = 2) -> np.ndarray:
+        a = np.asarray(a)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("resource amounts are integers")
+        if a.ndim != ndim:
+            raise ValueError(f"resource amounts are shaped (nres, n): got {a.shape}")
+        if a.size and (int(a.min()) < -(1 << 63) or int(a.max()) >= (1 << 63)):
+            raise ValueError("resource amounts are within int64")
+        return np.ascontiguousarray(a, np.int64)
+
+    def upload_node_resources(self, alloc, used=None) -> None:
+        """msh_upload_node_resources: alloc (and used, default zeros) shaped (nres, n), int64 in [0, 2^62], List
+        order. upload_nodes drops the table; patch_nodes and reset_node_pod_counts keep it; only
+        schedule_sequential_fit reads it and commits to used."""
+        alloc = self._amounts(alloc)
+        if used is not None:
+            used = self._amounts(used)
+            if used.shape != alloc.shape:
+                raise ValueError("alloc / used shape mismatch")
+        nres, n = alloc.shape
+        self._check(self._lib.msh_upload_node_resources(self.handle, n, nres, N.ptr(alloc), N.ptr(used)))
+
+    def patch_node_resources(self, idx, alloc=None, used=None) -> None:
+        """msh_patch_node_resources: alloc[:, k] / used[:, k] (shaped (nres, len(idx)); None keeps that array)
+        replace node idx[k]'s values. A patch of used accounts for a deleted pod, or for pods bound elsewhere."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        alloc = None if alloc is None else self._amounts(alloc)
+        used = None if used is None else self._amounts(used)
+        for a in (alloc, used):
+            if a is not None and a.shape[1] != len(idx):
+                raise ValueError("idx / values length mismatch")
+        self._check(self._lib.msh_patch_node_resources(self.handle, len(idx), N.ptr(idx), N.ptr(alloc), N.ptr(used)))
+
+    def clear_node_resources(self) -> None:
+        """msh_clear_node_resources: back to "no table"."""
+        self._check(self._lib.msh_clear_node_resources(self.handle))
+
+    def node_resources(self) -> tuple[np.ndarray, np.ndarray] | None:
+        """msh_node_resources: (alloc, used), each (nres, n) int64, or None when no table is present."""
+        present, nres = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.msh_node_resources(self.handle, C.byref(nres), None, None, C.byref(present)))
+        if not present.value:
+            return None
+        alloc = np.zeros((nres.value, self.n_nodes), np.int64)
+        used = np.zeros((nres.value, self.n_nodes), np.int64)
+        self._check(self._lib.msh_node_resources(self.handle, C.byref(nres), N.ptr(alloc), N.ptr(used),
+                                                 C.byref(present)))
+        return alloc, used
+
+    def schedule_sequential_fit(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_req, max_pods_per_node: int = 0,
+                                on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_fit: schedule_sequential with per-pod requests pod_req shaped (nres, p): a
+        node is feasible only while every requested amount fits alloc - used; a placement adds them to used."""
+        pod_digit = np.ascontiguousarray(pod_digit, np.int8)
+        pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
+        p = _same_len("schedule_sequential_fit", pod_digit, pod_tol)
+        pod_req = self._amounts(pod_req)
+        if pod_req.shape[1] != p:
+            raise ValueError("pod_req is shaped (nres, p)")
+        idx, score, status = self._outputs(p, out)
+        cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
+        self._check(self._lib.msh_schedule_sequential_fit(self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol),
+                                                          pod_req.shape[0], N.ptr(pod_req), int(max_pods_per_node),
+                                                          N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
+        return idx, score, status
+
+    def schedule_sequential_fit_device(self, p: int, d_pod_digit: int, d_pod_tol: int, nres: int, d_pod_req: int,
+                                       max_pods_per_node: int, d_idx: int, d_score: int, d_status: int,
+                                       stream: int = 0) -> None:
+        """msh_schedule_sequential_fit_device (asynchronous on `stream`; d_pod_req is not validated)."""
+        self._check(self._lib.msh_schedule_sequential_fit_device(self.handle, int(p), d_pod_digit, d_pod_tol, int(nres),
+                                                                 d_pod_req, int(max_pods_per_node), d_idx,
+                                                                 d_score or None, d_status, stream or None))
+
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):
     # ctypes argument conversion cost ~0.9 us per call next to a ~2.6 us launch.
@@ -484,12 +560,22 @@ class Scheduler:
     status.allocatable.pods of a k8s-shaped dict (snapshot.node_allocatable_pods). When any node of the
     snapshot carries one, schedule_sequential uploads the capacity column (None: INT32_MAX, in effect
     unlimited) and every node stops at its own limit; schedule_batch ignores it.
+
+    resources (default None: nothing changes) names the resources schedule_sequential accounts for, e.g.
+    ("cpu", "memory"), at most four: it then uploads the snapshot's status.allocatable amounts once per snapshot
+    (cpu in milli-units, everything else in units; a node lacking a value counts as 0) and places each pod only
+    where its requests (snapshot.pod_requests) still fit, committing them to the node (upstream's
+    NodeResourcesFit; DeviceContext.schedule_sequential_fit). schedule_batch ignores them.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
                  pre_score_plugins: Sequence[str] = (NODE_NUMBER,),
                  score_plugins: Sequence[ScorePluginConfig | str] = (NODE_NUMBER,),
-                 device: int = 0, ctx: DeviceContext | None = None, *, tie_break="first", tie_seed: int = 0):
+                 device: int = 0, ctx: DeviceContext | None = None, *, tie_break="first", tie_seed: int = 0,
+                 resources: Sequence[str] | None = None):
+        self.resources = None if resources is None else tuple(resources)
+        if self.resources is not None and not 1 <= len(self.resources) <= N.MAX_RESOURCES:
+            raise ValueError(f"resources: 1 to {N.MAX_RESOURCES} names")
         self.filter_plugins = list(filter_plugins)
         self.pre_score_plugins = list(pre_score_plugins)
         self.score_plugins = [c if isinstance(c, ScorePluginConfig) else ScorePluginConfig(c)
@@ -502,15 +588,22 @@ class Scheduler:
             self.ctx.set_tiebreak(tie_break, tie_seed)
         self.nodes: NodeTable | None = None
         self._cap_synced = False  # the snapshot's capacity column is on the device
+        self._res_synced = False  # the snapshot's allocatable amounts are on the device
+        self._node_objs: list[Any] = []  # the snapshot's nodes in List order (resources only)
 
     def close(self) -> None:
         self.ctx.close()
 
     # Replaces the per-cycle Nodes().List (minisched.go:40) with one device upload.
     def update_nodes(self, nodes: Iterable[Any]) -> NodeTable:
+        if self.resources is not None:
+            nodes = list(nodes)
         self.nodes = pack_nodes(nodes)
-        self.ctx.upload_nodes(self.nodes.unsched, self.nodes.digit)  # drops the device's capacity column
+        self.ctx.upload_nodes(self.nodes.unsched, self.nodes.digit)  # drops the device's capacity column and resources
         self._cap_synced = False
+        self._res_synced = False
+        if self.resources is not None:
+            self._node_objs = [nodes[i] for i in self.nodes.order]
         return self.nodes
 
     def _results(self, pods: PodTable, idx, score, status) -> list[ScheduleResult]:
@@ -549,9 +642,20 @@ class Scheduler:
             self.update_nodes(nodes)
         if self.nodes is None:
             raise N.MshError(N.MSH_ERR_STATE, "no node snapshot: call update_nodes() first")
+        if self.resources is not None:
+            pods = list(pods)
         table = pack_pods(pods)
         if self.nodes.allocatable_pods is not None and not self._cap_synced:
             self.ctx.upload_node_capacity(self.nodes.allocatable_pods)
             self._cap_synced = True
-        idx, score, status = self.ctx.schedule_sequential(table.digit, table.tolerates, max_pods_per_node)
+        if self.resources is None:
+            idx, score, status = self.ctx.schedule_sequential(table.digit, table.tolerates, max_pods_per_node)
+            return self._results(table, idx, score, status)
+        if not self._res_synced:
+            alloc = np.array([node_allocatable(n, self.resources) for n in self._node_objs], np.int64)
+            self.ctx.upload_node_resources(alloc.reshape(len(self._node_objs), len(self.resources)).T)
+            self._res_synced = True
+        req = np.array([pod_requests(p, self.resources) for p in pods], np.int64)
+        req = req.reshape(len(pods), len(self.resources)).T
+        idx, score, status = self.ctx.schedule_sequential_fit(table.digit, table.tolerates, req, max_pods_per_node)
         return self._results(table, idx, score, status)

@@ -12,6 +12,7 @@ dicts ({"metadata": {"name": ...}, "spec": {"unschedulable": ..., "tolerations":
 from __future__ import annotations
 
 import ctypes as C
+import re
 from dataclasses import dataclass
 from typing import Any, Iterable, Mapping, Sequence
 
@@ -52,6 +53,70 @@ def node_allocatable_pods(n: Any) -> int | None:
     if not 0 <= v <= N.INT32_MAX:
         raise ValueError(f"node {node_name(n)!r}: allocatable pods {v} outside [0, INT32_MAX]")
     return v
+
+
+_QUANTITY = re.compile(r"^([+-]?)(\d*)(?:\.(\d*))?(m|k|M|G|T|P|E|Ki|Mi|Gi|Ti|Pi|Ei)?$")
+_SUFFIX = {None: (1, 1), "m": (1, 1000),
+           **{s: (1000 ** (k + 1), 1) for k, s in enumerate(("k", "M", "G", "T", "P", "E"))},
+           **{s: (1024 ** (k + 1), 1) for k, s in enumerate(("Ki", "Mi", "Gi", "Ti", "Pi", "Ei"))}}
+RESOURCE_MAX = N.RESOURCE_MAX
+
+
+def parse_quantity(s: Any, milli: bool = False) -> int:
+    """A k8s resource.Quantity as an integer: its Value(), or with milli=True its MilliValue(), both rounded up
+    as upstream does ("1m" is 1 as a value, "0.5" is 500 milli). Accepts integers, plain and decimal numbers and
+    the suffixes m k M G T P E Ki Mi Gi Ti Pi Ei; exact integer arithmetic. Anything else raises ValueError."""
+    if isinstance(s, bool):
+        raise ValueError(f"not a quantity: {s!r}")
+    if isinstance(s, int):
+        return s * 1000 if milli else s
+    m = _QUANTITY.match(s.strip()) if isinstance(s, str) else None
+    if m is None or not (m.group(2) or m.group(3)):
+        raise ValueError(f"not a quantity: {s!r}")
+    sign, whole, frac, suffix = m.group(1), m.group(2) or "0", m.group(3) or "", m.group(4)
+    mul, div = _SUFFIX[suffix]
+    num = int(whole + frac) * mul * (1000 if milli else 1)
+    den = 10 ** len(frac) * div
+    if sign == "-":
+        return -(num // den)  # rounded up: towards zero for a negative amount
+    return -(-num // den)
+
+
+def _amount(v: Any, name: str, what: str) -> int:
+    q = 0 if v is None else parse_quantity(v, milli=(name == "cpu"))
+    if not 0 <= q <= RESOURCE_MAX:
+        raise ValueError(f"{what}: {name} = {v!r} outside [0, 2^62]")
+    return q
+
+
+def node_allocatable(n: Any, names: Sequence[str]) -> list[int]:
+    """The node's allocatable amount per resource name: status.allocatable of a k8s-shaped dict, or the attribute
+    `allocatable` (a mapping). cpu in milli-units, every other resource in units; a missing value counts as 0."""
+    table = n.allocatable if hasattr(n, "allocatable") else _get(n, "status", "allocatable")
+    table = table or {}
+    return [_amount(table.get(nm), nm, f"node {node_name(n)!r}") for nm in names]
+
+
+def _container_requests(c: Any, names: Sequence[str], what: str) -> list[int]:
+    req = _get(c, "resources", "requests") or {}
+    return [_amount(req.get(nm), nm, what) for nm in names]
+
+
+def pod_requests(p: Any, names: Sequence[str]) -> list[int]:
+    """The pod's request per resource name as NodeResourcesFit computes it: the sum over
+    spec.containers[].resources.requests, then the element-wise maximum with each init container (they run one at
+    a time, before the containers). Pod overhead is not included. Units as node_allocatable's."""
+    what = f"pod {pod_name(p)!r}"
+    spec = p if hasattr(p, "containers") else _get(p, "spec", default={})
+    total = [0] * len(names)
+    for c in _get(spec, "containers", default=()) or ():
+        total = [a + b for a, b in zip(total, _container_requests(c, names, what))]
+    for c in (_get(spec, "initContainers", default=None) or _get(spec, "init_containers", default=()) or ()):
+        total = [max(a, b) for a, b in zip(total, _container_requests(c, names, what))]
+    for nm, v in zip(names, total):
+        if v > RESOURCE_MAX:
+            raise ValueError(f"{what}: {nm} requests sum outside [0, 2^62]")
+    return total
 
 
 def pod_name(p: Any) -> str:
