@@ -696,6 +696,57 @@ func (x *Ctx) ScheduleSequentialFitDevice(p int, dPodDigit, dPodTol unsafe.Point
 	return nil
 }
 
+// ResourceScore is the resource-aware score of ScheduleSequentialFit (msh_resource_score).
+type ResourceScore int32
+
+const (
+	ResourceScoreNone           ResourceScore = C.MSH_RESOURCE_SCORE_NONE            // NodeNumber alone scores (the default)
+	ResourceScoreLeastAllocated ResourceScore = C.MSH_RESOURCE_SCORE_LEAST_ALLOCATED // NodeResourcesLeastAllocated: spread
+	ResourceScoreMostAllocated  ResourceScore = C.MSH_RESOURCE_SCORE_MOST_ALLOCATED  // NodeResourcesMostAllocated: pack
+)
+
+// SetResourceScore adds weight x the LeastAllocated / MostAllocated score of every feasible node to the totals of
+// ScheduleSequentialFit and its device form; resWeights holds one weight in [0, 100] per resource of the table (0:
+// fitted but not scored). Every other call ignores the setting, and it survives UploadNodes. Amounts must then stay
+// within 2^55. The library substitutes no defaults for a pod that requests nothing.
+func (x *Ctx) SetResourceScore(mode ResourceScore, weight int64, resWeights []int32) error {
+	w := make([]C.int32_t, len(resWeights))
+	for i, v := range resWeights {
+		w[i] = C.int32_t(v)
+	}
+	if rc := C.msh_set_resource_score(x.c, C.int32_t(mode), C.int64_t(weight), C.int32_t(len(w)), ptrI32(w)); rc != C.MSH_OK {
+		return x.lastErr("msh_set_resource_score", rc)
+	}
+	return nil
+}
+
+// ResourceScore returns the mode, the plugin weight and the resource weights the setting holds.
+func (x *Ctx) ResourceScore() (mode ResourceScore, weight int64, resWeights []int32, err error) {
+	var m, nr C.int32_t
+	var wt C.int64_t
+	w := make([]C.int32_t, int(C.MSH_MAX_RESOURCES))
+	if rc := C.msh_get_resource_score(x.c, &m, &wt, &nr, ptrI32(w)); rc != C.MSH_OK {
+		return ResourceScoreNone, 0, nil, x.lastErr("msh_get_resource_score", rc)
+	}
+	for i := 0; i < int(nr); i++ {
+		resWeights = append(resWeights, int32(w[i]))
+	}
+	return ResourceScore(m), int64(wt), resWeights, nil
+}
+
+// SeqFitMaxNodes returns the largest table ScheduleSequentialFit takes with nres resources, without or with a
+// resource score.
+func (x *Ctx) SeqFitMaxNodes(nres int, scored bool) (int, error) {
+	var out, sc C.int32_t
+	if scored {
+		sc = 1
+	}
+	if rc := C.msh_seq_fit_max_nodes(x.c, C.int32_t(nres), sc, &out); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_seq_fit_max_nodes", rc)
+	}
+	return int(out), nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

@@ -401,6 +401,58 @@ int msh_schedule_sequential_fit_device(msh_ctx* ctx, int32_t p, const int8_t* d_
                                        int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
                                        int32_t* d_out_status, void* stream);
 
+/* Resource-aware scoring for msh_schedule_sequential_fit / _fit_device (upstream's NodeResourcesLeastAllocated,
+ * noderesources/least_allocated.go, in the v1.22 default profile, and NodeResourcesMostAllocated,
+ * most_allocated.go, as a build extension in the same sense as the resource table; additive in ABI 8).
+ * The setting. msh_set_resource_score(ctx, mode, weight, nres, res_weights): mode NONE (the default: every call
+ *   behaves as without this section, kernel instance included; the other arguments are not read and may be 0 /
+ *   NULL), LEAST_ALLOCATED (spread: emptier nodes score higher) or MOST_ALLOCATED (pack). weight is the plugin
+ *   weight, in [1, 2^32] as a score weight of msh_set_plugins; nres in 1..MSH_MAX_RESOURCES; res_weights[r] in
+ *   [0, 100] with at least one positive. A resource of weight 0 is fitted but not scored (upstream's default
+ *   scores cpu and memory only). Anything else: MSH_ERR_INVALID. The setting is policy, like the plugin lists: it
+ *   survives msh_upload_nodes, msh_clear_node_resources and every patch. msh_get_resource_score returns it (every
+ *   out pointer may be NULL; out_res_weights takes MSH_MAX_RESOURCES values, 0 past nres).
+ * Semantics with a mode other than NONE, for pod j in order:
+ *   The feasible set and the status are exactly msh_schedule_sequential_fit's: MSH_FIT_ERROR with no feasible
+ *   node, otherwise MSH_SCORE_ERROR when NodeNumber scores without its PreScore state (commits nothing), otherwise
+ *   MSH_PLACED. For a feasible node i, total(i) = T(i) + weight * RS(j, i), where T(i) is the total the ctx's
+ *   plugin lists give it in msh_schedule_sequential_fit (NodeNumber at its weight, in every normalize mode over the
+ *   feasible list; 0 with an empty score list) and, in Go int64 arithmetic (division truncates; every operand is
+ *   non-negative), with q_r = used[r][i] + req[r][j] (used before this pod's commit: upstream's
+ *   calculateResourceAllocatableRequest adds the pod's request) and c_r = alloc[r][i]:
+ *     LEAST: s_r = (c_r == 0 || q_r > c_r) ? 0 : ((c_r - q_r) * 100) / c_r
+ *     MOST:  s_r = (c_r == 0 || q_r > c_r) ? 0 : (q_r * 100) / c_r
+ *     RS = (sum_r s_r * res_weights[r]) / (sum_r res_weights[r]), over the r of positive weight.
+ *   q_r > c_r happens for a zero request on a node whose alloc a patch lowered below used. The pod goes to the first
+ *   maximum of total in List order; out_score and commit_cb get that total; the commit is unchanged.
+ *   The library substitutes no "non-zero request" defaults: a caller that wants upstream's 100 milli-cpu / 200 MiB
+ *   for a pod that requests nothing puts them into pod_req.
+ * Range. (c - q) * 100 must stay inside int64, so a scored call needs every amount within
+ *   MSH_RESOURCE_SCORE_MAX = 2^55. The table is on the device only, so the ctx keeps the largest value any upload or
+ *   patch has written since the last msh_upload_node_resources; commits cannot exceed it (a positive request is
+ *   placed only where used + req <= alloc). While that bound is above the limit a scored call returns
+ *   MSH_ERR_UNSUPPORTED (the message names the limit). The host form returns MSH_ERR_INVALID for a request above
+ *   the limit; the device form does not validate, as before.
+ * Refusals of a scored call: nres of the setting != the table's: MSH_ERR_STATE; no table: MSH_ERR_STATE;
+ *   MSH_TIEBREAK_RANDOM and score-column lists: MSH_ERR_UNSUPPORTED; a table past the scored form's node limit:
+ *   MSH_ERR_UNSUPPORTED with the limit in the message. A node also keeps its allocatable amounts in registers, so
+ *   the scored limit is half the unscored one: 4,096 nodes for one or two resources, 2,048 for three or four.
+ *   msh_seq_fit_max_nodes reports the limit for a table of nres resources, unscored (scored = 0: 8,192 / 4,096)
+ *   or scored (scored != 0).
+ * Everything else ignores the setting, as it ignores the table: msh_schedule_sequential*, every batch, shard,
+ *   group and export entry point.
+ * A failed call changes nothing. */
+typedef enum msh_resource_score {
+  MSH_RESOURCE_SCORE_NONE = 0, /* default: every call behaves as without a resource score */
+  MSH_RESOURCE_SCORE_LEAST_ALLOCATED = 1,
+  MSH_RESOURCE_SCORE_MOST_ALLOCATED = 2
+} msh_resource_score;
+#define MSH_RESOURCE_SCORE_MAX ((int64_t)1 << 55)
+int msh_set_resource_score(msh_ctx* ctx, int32_t mode, int64_t weight, int32_t nres, const int32_t* res_weights);
+int msh_get_resource_score(const msh_ctx* ctx, int32_t* out_mode, int64_t* out_weight, int32_t* out_nres,
+                           int32_t* out_res_weights);
+int msh_seq_fit_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t scored, int32_t* out_max_nodes);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

@@ -52,6 +52,11 @@ INT32_MAX = 2**31 - 1  # a node capacity that is in effect unlimited (msh_upload
 MAX_RESOURCES = 4        # MSH_MAX_RESOURCES
 RESOURCE_MAX = 1 << 62   # MSH_RESOURCE_MAX: the largest allocatable / used / requested amount
 
+MSH_RESOURCE_SCORE_NONE = 0             # msh_set_resource_score: no resource score (the default)
+MSH_RESOURCE_SCORE_LEAST_ALLOCATED = 1  # NodeResourcesLeastAllocated: spread
+MSH_RESOURCE_SCORE_MOST_ALLOCATED = 2   # NodeResourcesMostAllocated: pack
+RESOURCE_SCORE_MAX = 1 << 55            # MSH_RESOURCE_SCORE_MAX: the largest amount a scored call takes
+
 MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
 MSH_TIEBREAK_RANDOM = 1  # seeded uniform choice among the maxima (msh_set_tiebreak)
 
@@ -67,6 +72,7 @@ EXPORTED = (
     "msh_upload_node_capacity", "msh_patch_node_capacity", "msh_clear_node_capacity", "msh_node_capacity",
     "msh_upload_node_resources", "msh_patch_node_resources", "msh_clear_node_resources", "msh_node_resources",
     "msh_schedule_sequential_fit", "msh_schedule_sequential_fit_device",
+    "msh_set_resource_score", "msh_get_resource_score", "msh_seq_fit_max_nodes",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -181,6 +187,9 @@ _SIGS = {
     "msh_node_resources": (C.c_int, [_P, C.POINTER(_I32), _P, _P, C.POINTER(_I32)]),
     "msh_schedule_sequential_fit": (C.c_int, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
     "msh_schedule_sequential_fit_device": (C.c_int, [_P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "msh_set_resource_score": (C.c_int, [_P, _I32, C.c_int64, _I32, _P]),
+    "msh_get_resource_score": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(C.c_int64), C.POINTER(_I32), _P]),
+    "msh_seq_fit_max_nodes": (C.c_int, [_P, _I32, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

@@ -891,6 +891,49 @@ int msh_get_tiebreak(const msh_ctx* c, int32_t* out_mode, uint64_t* out_seed, ui
   return MSH_OK;
 }
 
+int msh_set_resource_score(msh_ctx* c, int32_t mode, int64_t weight, int32_t nres, const int32_t* res_weights) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (mode == MSH_RESOURCE_SCORE_NONE) {  // the other arguments are not read
+    c->rs_mode = mode;
+    return MSH_OK;
+  }
+  if (mode != MSH_RESOURCE_SCORE_LEAST_ALLOCATED && mode != MSH_RESOURCE_SCORE_MOST_ALLOCATED)
+    return fail(c, MSH_ERR_INVALID, "resource score mode " + std::to_string(mode) +
+                                        ": not MSH_RESOURCE_SCORE_NONE (0), _LEAST_ALLOCATED (1) or _MOST_ALLOCATED (2)");
+  if (weight < 1 || weight > (int64_t(1) << 32)) return fail(c, MSH_ERR_INVALID, "resource score weight outside [1, 2^32]");
+  if (nres < 1 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [1, MSH_MAX_RESOURCES]");
+  if (!res_weights) return fail(c, MSH_ERR_INVALID, "null resource weights");
+  bool any = false;
+  for (int32_t r = 0; r < nres; ++r) {
+    if (res_weights[r] < 0 || res_weights[r] > 100)
+      return fail(c, MSH_ERR_INVALID, "resource weight outside [0, 100] at resource " + std::to_string(r));
+    any = any || res_weights[r] > 0;
+  }
+  if (!any) return fail(c, MSH_ERR_INVALID, "every resource weight is 0: nothing to score");
+  c->rs_mode = mode;
+  c->rs_weight = weight;
+  c->rs_nres = nres;
+  for (int32_t r = 0; r < MSH_MAX_RESOURCES; ++r) c->rs_w[r] = r < nres ? res_weights[r] : 0;
+  return MSH_OK;
+}
+
+int msh_get_resource_score(const msh_ctx* c, int32_t* out_mode, int64_t* out_weight, int32_t* out_nres,
+                           int32_t* out_res_weights) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_mode) *out_mode = c->rs_mode;
+  if (out_weight) *out_weight = c->rs_weight;
+  if (out_nres) *out_nres = c->rs_nres;
+  if (out_res_weights) std::copy(c->rs_w, c->rs_w + MSH_MAX_RESOURCES, out_res_weights);
+  return MSH_OK;
+}
+
+int msh_seq_fit_max_nodes(const msh_ctx* c, int32_t nres, int32_t scored, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 1 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = scored ? msh::seq_score_max_nodes(nres) : msh::seq_fit_max_nodes(nres);
+  return MSH_OK;
+}
+
 int msh_set_plugins(msh_ctx* c, const int32_t* filter_ids, int32_t nf, const int32_t* score_ids,
                     const int64_t* weights, int32_t ns) {
   // NodeNumber implements PreScore too (nodenumber.go:50), so it is its own prescore plugin.
@@ -1134,12 +1177,28 @@ struct FitReq {
 };
 
 // What a resource-fit call needs of the ctx, checked before any device work: a resource table of the call's
-// nres, within the kernel's table limit.
+// nres, within the kernel's table limit; with a resource score set (msh_set_resource_score) its own nres and table
+// limit, and every amount written into the table within MSH_RESOURCE_SCORE_MAX.
 int fit_check(msh_ctx* c, int32_t nres) {
   if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
   if (nres != c->nres)
     return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
                                         std::to_string(c->nres));
+  if (c->rs_mode != MSH_RESOURCE_SCORE_NONE) {
+    if (c->rs_nres != c->nres)
+      return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
+                                        " resources, the table has " + std::to_string(c->nres));
+    if (c->n_nodes > msh::seq_score_max_nodes(nres))
+      return fail(c, MSH_ERR_UNSUPPORTED,
+                  "the scored resource-fit form keeps the node state in registers: at most " +
+                      std::to_string(msh::seq_score_max_nodes(nres)) + " nodes per device with " +
+                      std::to_string(nres) + (nres == 1 ? " resource" : " resources"));
+    if (c->res_max > MSH_RESOURCE_SCORE_MAX)
+      return fail(c, MSH_ERR_UNSUPPORTED,
+                  "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
+                  "or patch wrote " + std::to_string(c->res_max));
+    return MSH_OK;
+  }
   if (c->n_nodes > msh::seq_fit_max_nodes(nres))
     return fail(c, MSH_ERR_UNSUPPORTED,
                 "the resource-fit form keeps the node state in registers: at most " +
@@ -1219,7 +1278,18 @@ int seq_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_dig
     f.used = c->d_used;
     f.pod_req = fit.d_pod_req;
     TimedLaunch tl(c);
-    e = msh::launch_seq_fit(f, s, &err);
+    if (c->rs_mode != MSH_RESOURCE_SCORE_NONE) {
+      msh::FitScoreArgs sa{};
+      sa.f = f;
+      sa.most = c->rs_mode == MSH_RESOURCE_SCORE_MOST_ALLOCATED ? 1 : 0;
+      sa.weight = c->rs_weight;
+      uint32_t sum = 0;
+      for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(sa.rw[r] = r < fit.nres ? c->rs_w[r] : 0);
+      sa.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
+      e = msh::launch_seq_score(sa, s, &err);
+    } else {
+      e = msh::launch_seq_fit(f, s, &err);
+    }
   } else {
     TimedLaunch tl(c);
     e = msh::launch_sequential(a, c->dev, s, &err);
@@ -1249,9 +1319,14 @@ int seq_host(msh_ctx* c, const char* entry, int32_t p, const int8_t* pod_digit, 
     if (max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
     if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
     if ((rc = fit_check(c, nres)) != MSH_OK) return rc;
-    for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e)
+    const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+    for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
       if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
         return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
+      if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
+        return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
+                                            std::to_string(e % (size_t)p));
+    }
   }
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
@@ -1456,6 +1531,7 @@ int msh_node_capacity(const msh_ctx* c, int32_t* out_cap, int32_t* out_present) 
 // through prep_stream behind the sequential launches in flight, which read the table at their start and write
 // `used` at their end, and finish before they return.
 namespace {
+int64_t res_values_max(const int64_t* v, size_t len) { return v && len ? *std::max_element(v, v + len) : 0; }
 bool res_values_ok(const int64_t* v, size_t len, size_t* bad) {
   for (size_t e = 0; e < len; ++e)
     if (v[e] < 0 || v[e] > MSH_RESOURCE_MAX) {
@@ -1520,6 +1596,7 @@ int msh_upload_node_resources(msh_ctx* c, int32_t n, int32_t nres, const int64_t
   MSH_HIP(c, hipStreamSynchronize(ps));
   c->nres = nres;
   c->have_res = true;
+  c->res_max = std::max(res_values_max(alloc, len), res_values_max(used, len));
   return MSH_OK;
 }
 
@@ -1558,6 +1635,8 @@ int msh_patch_node_resources(msh_ctx* c, int32_t count, const int32_t* idx, cons
   hipError_t e = msh::launch_res_patch(si, alloc ? sa : nullptr, used ? su : nullptr, count, c->nres,
                                        (int64_t)c->res_cap, c->d_alloc, c->d_used, c->prep_stream);
   if (e != hipSuccess) return hip_fail(c, e, "res_patch_kernel");
+  // from here the values may be in the table: the bound covers them whatever the stream reports
+  c->res_max = std::max(c->res_max, std::max(res_values_max(alloc, len), res_values_max(used, len)));
   MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
   return MSH_OK;
 }

@@ -91,6 +91,16 @@ struct msh_ctx {
   int32_t res_rows = 0;  // rows allocated (>= nres)
   int32_t nres = 0;
   bool have_res = false;
+  // the resource score of msh_schedule_sequential_fit (msh_set_resource_score; policy, like the plugin lists: it
+  // outlives tables): mode, plugin weight, the resources it was set for and their weights. res_max: the largest
+  // amount any upload or patch has written into the table since the last msh_upload_node_resources (the table
+  // itself is on the device only), which bounds every alloc and used whatever was committed since: a scored
+  // call needs it within MSH_RESOURCE_SCORE_MAX
+  int32_t rs_mode = MSH_RESOURCE_SCORE_NONE;
+  int64_t rs_weight = 1;
+  int32_t rs_nres = 0;
+  int32_t rs_w[MSH_MAX_RESOURCES] = {};
+  int64_t res_max = 0;
   // per caller stream, the event of its last sequential launch: an alias of a table version's reader
   // event (not owned here; track_launch)
   std::vector<std::pair<hipStream_t, hipEvent_t>> seq_inflight;

@@ -69,6 +69,21 @@ __device__ __forceinline__ void decode_pod(int64_t im, int64_t ix, int64_t ia, b
   *out_status = st;
 }
 
+// decode_pod by class, for a scorer that adds a per-node term to NodeNumber's (msh_seq_score.hip): status, and
+// the NodeNumber total of a feasible match (*tm) and of a feasible non-match (*tx), given which of the two
+// classes hold a feasible node. In every normalize mode the class decode_pod does not select scores 0 (raw 0,
+// DefaultNormalizeScore's 100 * 0 / max, reverse's 100 - 100, min-max's minimum), so the selected class takes
+// decode_pod's score and the other 0.
+__device__ __forceinline__ void decode_classes(bool has_m, bool has_x, bool pd_valid, const PluginParams& pp,
+                                               int64_t* tm, int64_t* tx, int32_t* out_status) {
+  int32_t sel;
+  int64_t sc;
+  decode_pod(has_m ? 0 : -1, has_x ? 1 : -1, has_m ? 0 : (has_x ? 1 : -1), pd_valid, pp, &sel, &sc, out_status);
+  const bool m_wins = has_m && sel == 0;
+  *tm = m_wins ? sc : 0;
+  *tx = m_wins ? 0 : sc;
+}
+
 // decode_pod for the identity-like modes (NONE, DEFAULT: everything that does not need the first
 // feasible non-match), as selects on launch-constant flags instead of a branch per mode.
 struct IdentDecode {

@@ -288,6 +288,18 @@ struct FitArgs {
 // Nodes the resource-fit kernel holds for a table of nres resources (8,192 up to two, 4,096 for three or four).
 int32_t seq_fit_max_nodes(int32_t nres);
 hipError_t launch_seq_fit(const FitArgs& a, hipStream_t s, std::string* err);
+// The scored resource-fit form (msh_seq_score.hip; msh_set_resource_score with a mode other than NONE): the same
+// loop, with upstream's NodeResourcesLeastAllocated / MostAllocated score of every feasible node added to the
+// NodeNumber total, so each pod is a true arg-max over the table. Every amount must be <= 2^55 (checked on the host).
+struct FitScoreArgs {
+  FitArgs f;
+  int32_t most;             // 0: LeastAllocated, 1: MostAllocated
+  int64_t weight;           // the plugin weight, [1, 2^32]
+  int32_t rw[FIT_MAX_RES];  // resource weights in [0, 100], 0 for a resource that is not scored and for r >= f.nres
+  uint32_t wsum_magic;      // ceil(2^31 / sum of rw): x / sum = (x * magic) >> 31 exactly for x <= 100 * sum
+};
+int32_t seq_score_max_nodes(int32_t nres);
+hipError_t launch_seq_score(const FitScoreArgs& a, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

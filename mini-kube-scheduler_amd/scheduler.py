@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 import weakref
 from dataclasses import dataclass
-from typing import Any, Callable, Iterable, Sequence
+from typing import Any, Callable, Iterable, Mapping, Sequence
 
 import numpy as np
 
@@ -34,6 +34,11 @@ PRESCORE_IDS = {NODE_NUMBER: N.MSH_PLUGIN_NODE_NUMBER}
 # msh_tiebreak by name and by value (DeviceContext.set_tiebreak, Scheduler(tie_break=...))
 TIEBREAK_MODES = {"first": N.MSH_TIEBREAK_FIRST, "random": N.MSH_TIEBREAK_RANDOM,
                   N.MSH_TIEBREAK_FIRST: N.MSH_TIEBREAK_FIRST, N.MSH_TIEBREAK_RANDOM: N.MSH_TIEBREAK_RANDOM}
+# msh_resource_score by name and by value (DeviceContext.set_resource_score, Scheduler(resource_score=...))
+RESOURCE_SCORE_MODES = {"none": N.MSH_RESOURCE_SCORE_NONE, "least": N.MSH_RESOURCE_SCORE_LEAST_ALLOCATED,
+                        "most": N.MSH_RESOURCE_SCORE_MOST_ALLOCATED,
+                        **{v: v for v in (N.MSH_RESOURCE_SCORE_NONE, N.MSH_RESOURCE_SCORE_LEAST_ALLOCATED,
+                                          N.MSH_RESOURCE_SCORE_MOST_ALLOCATED)}}
 _U64 = (1 << 64) - 1
 
 
@@ -374,6 +379,44 @@ class DeviceContext:
                                                                  d_pod_req, int(max_pods_per_node), d_idx,
                                                                  d_score or None, d_status, stream or None))
 
+    # -- resource-aware scoring of schedule_sequential_fit (NodeResourcesLeastAllocated / MostAllocated) --
+    def set_resource_score(self, mode, weight: int = 1, resource_weights=None) -> None:
+        """msh_set_resource_score: "none" (the default), "least" (spread: emptier nodes score higher) or "most"
+        (pack), or the integers MSH_RESOURCE_SCORE_*. weight is the plugin weight; resource_weights one weight in
+        [0, 100] per resource of the table (0: fitted but not scored), None = 1 for each resource of the table
+        now on the device. Only schedule_sequential_fit / _fit_device read the setting; it survives
+        upload_nodes."""
+        m = RESOURCE_SCORE_MODES.get(mode) if isinstance(mode, (str, int)) and not isinstance(mode, bool) else None
+        if m is None:
+            raise N.MshError(N.MSH_ERR_INVALID, f"resource score mode {mode!r}: not 'none' (0), 'least' (1) or 'most' (2)")
+        if m == N.MSH_RESOURCE_SCORE_NONE:
+            self._check(self._lib.msh_set_resource_score(self.handle, m, 0, 0, None))
+            return
+        if resource_weights is None:
+            present, nres = C.c_int32(0), C.c_int32(0)
+            self._check(self._lib.msh_node_resources(self.handle, C.byref(nres), None, None, C.byref(present)))
+            if not present.value:
+                raise N.MshError(N.MSH_ERR_STATE, "resource_weights=None takes the table's resources: no table is present")
+            resource_weights = [1] * nres.value
+        w = np.ascontiguousarray(resource_weights, np.int32)
+        if w.ndim != 1:
+            raise ValueError("resource_weights: one weight per resource")
+        self._check(self._lib.msh_set_resource_score(self.handle, m, int(weight), len(w), N.ptr(w)))
+
+    def resource_score(self) -> tuple[int, int, list[int]]:
+        """msh_get_resource_score: (mode, weight, the resource weights it was set with)."""
+        m, w, nres = C.c_int32(), C.c_int64(), C.c_int32()
+        rw = np.zeros(N.MAX_RESOURCES, np.int32)
+        self._check(self._lib.msh_get_resource_score(self.handle, C.byref(m), C.byref(w), C.byref(nres), N.ptr(rw)))
+        return m.value, w.value, rw[: nres.value].tolist()
+
+    def seq_fit_max_nodes(self, nres: int, scored: bool = False) -> int:
+        """msh_seq_fit_max_nodes: the largest table schedule_sequential_fit takes with nres resources, without
+        (scored=False) or with a resource score."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_fit_max_nodes(self.handle, int(nres), 1 if scored else 0, C.byref(out)))
+        return out.value
+
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):
     # ctypes argument conversion cost ~0.9 us per call next to a ~2.6 us launch.
@@ -566,16 +609,24 @@ class Scheduler:
     (cpu in milli-units, everything else in units; a node lacking a value counts as 0) and places each pod only
     where its requests (snapshot.pod_requests) still fit, committing them to the node (upstream's
     NodeResourcesFit; DeviceContext.schedule_sequential_fit). schedule_batch ignores them.
+
+    resource_score ("least" or "most"; default None: NodeNumber alone scores) adds upstream's
+    NodeResourcesLeastAllocated (spread) or NodeResourcesMostAllocated (pack) score of the pod's requests against
+    each feasible node to schedule_sequential's totals, at plugin weight resource_score_weight. resource_weights
+    is a mapping from resource name to weight, or a sequence aligned with `resources` (default: 1 each; 0: fitted
+    but not scored). It needs `resources`. The library substitutes no defaults for pods that request nothing.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
                  pre_score_plugins: Sequence[str] = (NODE_NUMBER,),
                  score_plugins: Sequence[ScorePluginConfig | str] = (NODE_NUMBER,),
                  device: int = 0, ctx: DeviceContext | None = None, *, tie_break="first", tie_seed: int = 0,
-                 resources: Sequence[str] | None = None):
+                 resources: Sequence[str] | None = None, resource_score=None, resource_score_weight: int = 1,
+                 resource_weights=None):
         self.resources = None if resources is None else tuple(resources)
         if self.resources is not None and not 1 <= len(self.resources) <= N.MAX_RESOURCES:
             raise ValueError(f"resources: 1 to {N.MAX_RESOURCES} names")
+        rs_weights = self._resource_weights(self.resources, resource_score, resource_weights)
         self.filter_plugins = list(filter_plugins)
         self.pre_score_plugins = list(pre_score_plugins)
         self.score_plugins = [c if isinstance(c, ScorePluginConfig) else ScorePluginConfig(c)
@@ -586,10 +637,39 @@ class Scheduler:
         # ties uniformly as the reference does (schedule_sequential then raises MSH_ERR_UNSUPPORTED)
         if tie_break not in ("first", N.MSH_TIEBREAK_FIRST) or tie_seed:
             self.ctx.set_tiebreak(tie_break, tie_seed)
+        if rs_weights is not None:
+            self.ctx.set_resource_score(resource_score, resource_score_weight, rs_weights)
         self.nodes: NodeTable | None = None
         self._cap_synced = False  # the snapshot's capacity column is on the device
         self._res_synced = False  # the snapshot's allocatable amounts are on the device
         self._node_objs: list[Any] = []  # the snapshot's nodes in List order (resources only)
+
+    @staticmethod
+    def _resource_weights(resources, resource_score, resource_weights) -> list[int] | None:
+        """The weights aligned with `resources` for a resource score, None without one (argument errors:
+        ValueError, before any device work)."""
+        if resource_score is None:
+            if resource_weights is not None:
+                raise ValueError("resource_weights without resource_score")
+            return None
+        if resource_score not in RESOURCE_SCORE_MODES or isinstance(resource_score, bool):
+            raise ValueError(f"resource_score {resource_score!r}: not 'none', 'least' or 'most'")
+        if resources is None:
+            raise ValueError("resource_score needs resources")
+        if resource_weights is None:
+            return [1] * len(resources)
+        if isinstance(resource_weights, Mapping):
+            unknown = set(resource_weights) - set(resources)
+            if unknown:
+                raise ValueError(f"resource_weights names {sorted(unknown)}, not among resources {list(resources)}")
+            w = [int(resource_weights.get(r, 0)) for r in resources]
+        else:
+            w = [int(x) for x in resource_weights]
+            if len(w) != len(resources):
+                raise ValueError("resource_weights: one weight per resource")
+        if any(not 0 <= x <= 100 for x in w) or not any(w):
+            raise ValueError("resource_weights: each in [0, 100], at least one positive")
+        return w
 
     def close(self) -> None:
         self.ctx.close()
