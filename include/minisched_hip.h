@@ -453,6 +453,74 @@ int msh_get_resource_score(const msh_ctx* ctx, int32_t* out_mode, int64_t* out_w
                            int32_t* out_res_weights);
 int msh_seq_fit_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t scored, int32_t* out_max_nodes);
 
+/* Pod topology spread for sequential-commit mode (upstream's PodTopologySpread filter with whenUnsatisfiable:
+ * DoNotSchedule, in the v1.22 default profile, as a build extension in the same sense as the resource table;
+ * additive in ABI 8). It is the one constraint here in which a commit changes the verdict of many nodes at once:
+ * every node of the chosen zone and, through the minimum, every node of every zone.
+ * The zone column. zone[i], one int32 per uploaded node in List order: a zone id in [0, MSH_MAX_ZONES), or -1 for a
+ *   node that lacks the topology key. Zset is the set of ids that occur on at least one node. It is fixed by the
+ *   upload: it does not depend on cordons, capacities or free resources (upstream's minimum runs over domains, not
+ *   over feasible nodes).
+ * Spread groups. G groups, 0 <= G <= MSH_MAX_SPREAD_GROUPS, each with max_skew[g] in [1, INT32_MAX]. A group is one
+ *   (selector, constraint) pair: a pod of group g both matches the selector and carries the constraint (the
+ *   Deployment case, upstream's selfMatchNum = 1).
+ * Spread counts. cnt[g][z], int32: the committed pods of group g on nodes of zone z. Ctx state like the pod counts
+ *   and used: unversioned, carried from call to call.
+ * msh_schedule_sequential_spread / _spread_device: msh_schedule_sequential_fit with one more per-pod input,
+ *   pod_group[j] in [-1, G). Pods are decided strictly in order. For a pod of group -1 everything is exactly
+ *   _fit's. For a pod of group g >= 0 node i is feasible iff it is feasible for _fit (filter list, count[i] <
+ *   eff[i], requests), zone[i] >= 0, and cnt[g][zone[i]] + 1 - minc(g) <= max_skew[g], where minc(g) is the minimum
+ *   of cnt[g][z] over the z of Zset. With Zset empty no node is feasible for a grouped pod. Status, score, the
+ *   first-maximum tie-break over the feasible set and the commit are _fit's; a MSH_PLACED pod of group g >= 0 also
+ *   adds 1 to cnt[g][zone[sel]]. MSH_FIT_ERROR and MSH_SCORE_ERROR commit nothing.
+ * The resource table is optional here: nres = 0 (pod_req may be NULL) checks and commits no requests, with or
+ *   without a table on the ctx; nres > 0 behaves as in _fit and must equal the table's.
+ * Everything else ignores zones, groups and spread counts: msh_schedule_sequential*, _fit*, and every batch, shard,
+ *   group and export entry point make no spread commit and apply no spread check.
+ * Refusals of a spread call. No zone column: MSH_ERR_STATE (as no node table, and no resource table with nres > 0).
+ *   Host form: a group outside [-1, G) (so any group >= 0 with G = 0), a request outside [0, 2^62]:
+ *   MSH_ERR_INVALID. MSH_TIEBREAK_RANDOM, a score-column list, a resource score other than NONE:
+ *   MSH_ERR_UNSUPPORTED with a message that names the reason (scoring together with spread is not implemented). A
+ *   table past the limit: MSH_ERR_UNSUPPORTED with the limit in the message. The limits are _fit's: 8,192 nodes
+ *   for up to two resources, 4,096 for three or four; msh_seq_spread_max_nodes reports them for nres in 0..4.
+ * The device form is asynchronous, as msh_schedule_sequential_fit_device, and validates neither d_pod_req nor
+ *   d_pod_group: the kernel treats every group value outside [0, G) as -1, an ungrouped pod.
+ * Lifetime. msh_upload_nodes drops the zone column and zeroes the spread counts (the groups, policy like the plugin
+ *   lists, stay). msh_upload_node_zones replaces the column and zeroes the counts: a node's zone changed under its
+ *   pods. msh_set_spread_groups replaces G and max_skew and zeroes the counts when G changes; with the same G it
+ *   only updates the skews. msh_patch_nodes, msh_reset_node_pod_counts and the capacity and resource writers keep
+ *   all of it. The writers and readers are synchronous, ordered after the ctx's sequential launches in flight, and
+ *   do not rebuild the node table.
+ * msh_upload_node_zones: n != the uploaded node count, a value outside [-1, MSH_MAX_ZONES): MSH_ERR_INVALID; before
+ *   msh_upload_nodes: MSH_ERR_STATE. msh_clear_node_zones: back to "no column" (the counts stay until the next
+ *   upload). msh_node_zones: *out_present and, with a column, its n values in out_zone (may be NULL).
+ * msh_set_spread_groups: G outside [0, MSH_MAX_SPREAD_GROUPS], a skew below 1: MSH_ERR_INVALID.
+ *   msh_get_spread_groups: *out_G and the G skews (each pointer may be NULL).
+ * msh_spread_counts: the G * MSH_MAX_ZONES counts, out_cnt[g * MSH_MAX_ZONES + z] (nothing is written with G = 0).
+ * msh_patch_spread_counts: value[k] replaces cnt[g[k]][z[k]]: how a caller accounts for a deleted pod, or for pods
+ *   bound before the scheduler started. g in [0, G), z in [0, MSH_MAX_ZONES), value >= 0, the (g, z) pairs pairwise
+ *   distinct (MSH_ERR_INVALID otherwise). msh_reset_spread_counts: every count to 0.
+ * A failed call changes nothing. */
+#define MSH_MAX_ZONES 64
+#define MSH_MAX_SPREAD_GROUPS 128
+int msh_upload_node_zones(msh_ctx* ctx, int32_t n, const int32_t* zone);
+int msh_clear_node_zones(msh_ctx* ctx);
+int msh_node_zones(const msh_ctx* ctx, int32_t* out_zone, int32_t* out_present);
+int msh_set_spread_groups(msh_ctx* ctx, int32_t G, const int32_t* max_skew);
+int msh_get_spread_groups(const msh_ctx* ctx, int32_t* out_G, int32_t* out_max_skew);
+int msh_spread_counts(msh_ctx* ctx, int32_t* out_cnt);
+int msh_patch_spread_counts(msh_ctx* ctx, int32_t count, const int32_t* g, const int32_t* z, const int32_t* value);
+int msh_reset_spread_counts(msh_ctx* ctx);
+int msh_seq_spread_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t* out_max_nodes);
+int msh_schedule_sequential_spread(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                   const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
+                                   int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+                                   int32_t* out_status, msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_spread_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit,
+                                          const uint8_t* d_pod_tol, const int32_t* d_pod_group, int32_t nres,
+                                          const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
+                                          int64_t* d_out_score, int32_t* d_out_status, void* stream);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

@@ -57,6 +57,9 @@ MSH_RESOURCE_SCORE_LEAST_ALLOCATED = 1  # NodeResourcesLeastAllocated: spread
 MSH_RESOURCE_SCORE_MOST_ALLOCATED = 2   # NodeResourcesMostAllocated: pack
 RESOURCE_SCORE_MAX = 1 << 55            # MSH_RESOURCE_SCORE_MAX: the largest amount a scored call takes
 
+MAX_ZONES = 64           # MSH_MAX_ZONES: zone ids are in [0, MAX_ZONES), -1 = the node has no zone
+MAX_SPREAD_GROUPS = 128  # MSH_MAX_SPREAD_GROUPS
+
 MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
 MSH_TIEBREAK_RANDOM = 1  # seeded uniform choice among the maxima (msh_set_tiebreak)
 
@@ -73,6 +76,9 @@ EXPORTED = (
     "msh_upload_node_resources", "msh_patch_node_resources", "msh_clear_node_resources", "msh_node_resources",
     "msh_schedule_sequential_fit", "msh_schedule_sequential_fit_device",
     "msh_set_resource_score", "msh_get_resource_score", "msh_seq_fit_max_nodes",
+    "msh_upload_node_zones", "msh_clear_node_zones", "msh_node_zones", "msh_set_spread_groups",
+    "msh_get_spread_groups", "msh_spread_counts", "msh_patch_spread_counts", "msh_reset_spread_counts",
+    "msh_seq_spread_max_nodes", "msh_schedule_sequential_spread", "msh_schedule_sequential_spread_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -190,6 +196,17 @@ _SIGS = {
     "msh_set_resource_score": (C.c_int, [_P, _I32, C.c_int64, _I32, _P]),
     "msh_get_resource_score": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(C.c_int64), C.POINTER(_I32), _P]),
     "msh_seq_fit_max_nodes": (C.c_int, [_P, _I32, _I32, C.POINTER(_I32)]),
+    "msh_upload_node_zones": (C.c_int, [_P, _I32, _P]),
+    "msh_clear_node_zones": (C.c_int, [_P]),
+    "msh_node_zones": (C.c_int, [_P, _P, C.POINTER(_I32)]),
+    "msh_set_spread_groups": (C.c_int, [_P, _I32, _P]),
+    "msh_get_spread_groups": (C.c_int, [_P, C.POINTER(_I32), _P]),
+    "msh_spread_counts": (C.c_int, [_P, _P]),
+    "msh_patch_spread_counts": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "msh_reset_spread_counts": (C.c_int, [_P]),
+    "msh_seq_spread_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
+    "msh_schedule_sequential_spread": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_spread_device": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

@@ -35,6 +35,7 @@ SOURCES = [
     ("msh_seq_cap.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_fit.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_score.hip", "hipcc", ["-x", "hip"]),
+    ("msh_seq_spread.hip", "hipcc", ["-x", "hip"]),
     ("msh_prep.hip", "hipcc", ["-x", "hip"]),
     ("msh_capi.cpp", "hipcc", []),
     ("msh_shard.cpp", "hipcc", []),

@@ -402,6 +402,8 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
     if ((rc = after_seq(c)) != MSH_OK) return rc;
     MSH_HIP(c, hipMemsetAsync(c->d_counts, 0, (size_t)c->counts_replicas * c->counts_cap * sizeof(int32_t), ps));
     c->counts_dirty = false;
+    if (c->d_spread_cnt)  // the spread counts belonged to the previous table's nodes
+      MSH_HIP(c, hipMemsetAsync(c->d_spread_cnt, 0, (size_t)MSH_MAX_SPREAD_GROUPS * MSH_MAX_ZONES * sizeof(int32_t), ps));
   }
   MSH_HIP(c, hipStreamSynchronize(ps));
   if (up) {  // the capacity column belonged to the previous table's nodes
@@ -409,6 +411,9 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
     c->h_cap.clear();
     c->have_res = false;  // and so did the resource table
     c->nres = 0;
+    c->have_zone = false;  // and the zone column
+    c->h_zone.clear();
+    c->zset = 0;
   }
   c->cur = s;
   c->n_nodes = n;
@@ -796,6 +801,9 @@ void msh_destroy(msh_ctx* c) {
   (void)hipFree(c->d_cap);
   (void)hipFree(c->d_alloc);
   (void)hipFree(c->d_used);
+  (void)hipFree(c->d_zone);
+  (void)hipFree(c->d_skew);
+  (void)hipFree(c->d_spread_cnt);
   for (hipEvent_t e : c->async_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->tev) {
@@ -1668,6 +1676,325 @@ int msh_node_resources(msh_ctx* c, int32_t* out_nres, int64_t* out_alloc, int64_
                                 hipMemcpyDeviceToHost, c->prep_stream));
   }
   MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+
+// Topology spread (msh_schedule_sequential_spread): the zone column, the groups and the counts cnt[g][z]. None of
+// it is versioned; the writers and readers go through prep_stream behind the sequential launches in flight, which
+// read all of it at their start and write the counts at their end, and finish before they return.
+namespace {
+constexpr size_t SPREAD_CNT_BYTES = (size_t)MSH_MAX_SPREAD_GROUPS * MSH_MAX_ZONES * sizeof(int32_t);
+
+// d_skew and d_spread_cnt: allocated whole and zeroed at first use
+int spread_alloc(msh_ctx* c) {
+  if (!c->d_skew) MSH_HIP(c, hipMalloc(&c->d_skew, MSH_MAX_SPREAD_GROUPS * sizeof(int32_t)));
+  if (c->d_spread_cnt) return MSH_OK;
+  int32_t* cn = nullptr;
+  MSH_HIP(c, hipMalloc(&cn, SPREAD_CNT_BYTES));
+  hipError_t e = hipMemsetAsync(cn, 0, SPREAD_CNT_BYTES, c->prep_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->prep_stream);
+  if (e != hipSuccess) {
+    (void)hipFree(cn);
+    return hip_fail(c, e, "spread counts");
+  }
+  c->d_spread_cnt = cn;
+  return MSH_OK;
+}
+
+int spread_zero_counts(msh_ctx* c) {
+  MSH_HIP(c, hipMemsetAsync(c->d_spread_cnt, 0, SPREAD_CNT_BYTES, c->prep_stream));
+  return MSH_OK;
+}
+}  // namespace
+
+int msh_upload_node_zones(msh_ctx* c, int32_t n, const int32_t* zone) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (n != c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "zone column of " + std::to_string(n) + " entries for " +
+                                        std::to_string(c->n_nodes) + " uploaded nodes");
+  if (n > 0 && !zone) return fail(c, MSH_ERR_INVALID, "null zone array");
+  uint64_t zset = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    if (zone[i] < -1 || zone[i] >= MSH_MAX_ZONES)
+      return fail(c, MSH_ERR_INVALID, "zone outside [-1, MSH_MAX_ZONES) at node " + std::to_string(i));
+    if (zone[i] >= 0) zset |= uint64_t(1) << zone[i];
+  }
+  DeviceGuard g(c->device);
+  int rc = spread_alloc(c);
+  if (rc != MSH_OK) return rc;
+  if ((size_t)c->n_pad > c->zone_cap) {
+    int32_t* dz = nullptr;
+    MSH_HIP(c, hipMalloc(&dz, (size_t)c->n_pad * sizeof(int32_t)));
+    wait_events(c->seq_inflight);
+    (void)hipFree(c->d_zone);
+    c->d_zone = dz;
+    c->zone_cap = (size_t)c->n_pad;
+    c->have_zone = false;
+  }
+  if ((rc = after_seq(c)) != MSH_OK) return rc;
+  const size_t bytes = (size_t)c->n_pad * sizeof(int32_t);
+  if ((rc = node_stage(c, bytes)) != MSH_OK) return rc;
+  c->have_zone = false;  // a failed copy leaves no column
+  int32_t* st = reinterpret_cast<int32_t*>(c->h_nstage);
+  std::fill(st, st + c->n_pad, -1);  // the padding slots never hold a node
+  if (n > 0) std::copy(zone, zone + n, st);
+  MSH_HIP(c, hipMemcpyAsync(c->d_zone, st, bytes, hipMemcpyHostToDevice, c->prep_stream));
+  if ((rc = spread_zero_counts(c)) != MSH_OK) return rc;  // a node's zone changed under its pods
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  c->h_zone.assign(zone, zone + n);
+  c->zset = zset;
+  c->have_zone = true;
+  return MSH_OK;
+}
+
+int msh_clear_node_zones(msh_ctx* c) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  c->have_zone = false;  // launches in flight keep reading the device column, which stays allocated
+  c->h_zone.clear();
+  c->zset = 0;
+  return MSH_OK;
+}
+
+int msh_node_zones(const msh_ctx* c, int32_t* out_zone, int32_t* out_present) {
+  if (!c || !out_present) return MSH_ERR_INVALID;
+  *out_present = c->have_zone ? 1 : 0;
+  if (c->have_zone && out_zone) std::copy(c->h_zone.begin(), c->h_zone.end(), out_zone);
+  return MSH_OK;
+}
+
+int msh_set_spread_groups(msh_ctx* c, int32_t G, const int32_t* max_skew) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (G < 0 || G > MSH_MAX_SPREAD_GROUPS) return fail(c, MSH_ERR_INVALID, "G outside [0, MSH_MAX_SPREAD_GROUPS]");
+  if (G > 0 && !max_skew) return fail(c, MSH_ERR_INVALID, "null max_skew array");
+  for (int32_t k = 0; k < G; ++k)
+    if (max_skew[k] < 1) return fail(c, MSH_ERR_INVALID, "max_skew below 1 at group " + std::to_string(k));
+  DeviceGuard g(c->device);
+  int rc = spread_alloc(c);
+  if (rc != MSH_OK) return rc;
+  if ((rc = after_seq(c)) != MSH_OK) return rc;
+  if (G > 0) {
+    if ((rc = node_stage(c, (size_t)G * sizeof(int32_t))) != MSH_OK) return rc;
+    std::memcpy(c->h_nstage, max_skew, (size_t)G * sizeof(int32_t));
+    MSH_HIP(c, hipMemcpyAsync(c->d_skew, c->h_nstage, (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice,
+                              c->prep_stream));
+  }
+  if (G != c->sp_groups && (rc = spread_zero_counts(c)) != MSH_OK) return rc;  // the rows mean other groups now
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  c->sp_groups = G;
+  c->h_skew.assign(max_skew, max_skew + G);
+  return MSH_OK;
+}
+
+int msh_get_spread_groups(const msh_ctx* c, int32_t* out_G, int32_t* out_max_skew) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_G) *out_G = c->sp_groups;
+  if (out_max_skew) std::copy(c->h_skew.begin(), c->h_skew.end(), out_max_skew);
+  return MSH_OK;
+}
+
+int msh_spread_counts(msh_ctx* c, int32_t* out_cnt) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (c->sp_groups == 0) return MSH_OK;
+  if (!out_cnt) return fail(c, MSH_ERR_INVALID, "null output");
+  DeviceGuard g(c->device);
+  int rc = after_seq(c);  // sequential launches of this ctx in flight update the counts
+  if (rc != MSH_OK) return rc;
+  MSH_HIP(c, hipMemcpyAsync(out_cnt, c->d_spread_cnt, (size_t)c->sp_groups * MSH_MAX_ZONES * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, c->prep_stream));
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+
+int msh_patch_spread_counts(msh_ctx* c, int32_t count, const int32_t* gi, const int32_t* zi, const int32_t* value) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
+  if (count == 0) return MSH_OK;
+  if (!gi || !zi || !value) return fail(c, MSH_ERR_INVALID, "null patch arrays");
+  std::vector<int32_t> keys((size_t)count);
+  for (int32_t k = 0; k < count; ++k) {
+    if (gi[k] < 0 || gi[k] >= c->sp_groups)
+      return fail(c, MSH_ERR_INVALID, "group outside [0, G) at patch entry " + std::to_string(k));
+    if (zi[k] < 0 || zi[k] >= MSH_MAX_ZONES)
+      return fail(c, MSH_ERR_INVALID, "zone outside [0, MSH_MAX_ZONES) at patch entry " + std::to_string(k));
+    if (value[k] < 0) return fail(c, MSH_ERR_INVALID, "negative count at patch entry " + std::to_string(k));
+    keys[(size_t)k] = gi[k] * MSH_MAX_ZONES + zi[k];
+  }
+  std::vector<int32_t> sorted(keys);
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return fail(c, MSH_ERR_INVALID, "duplicate (group, zone) pair");
+  DeviceGuard g(c->device);
+  int rc = after_seq(c);
+  if (rc != MSH_OK) return rc;
+  // the table (32 KB) through the page-locked stage: read, patched on the host, written back
+  if ((rc = node_stage(c, SPREAD_CNT_BYTES)) != MSH_OK) return rc;
+  int32_t* st = reinterpret_cast<int32_t*>(c->h_nstage);
+  MSH_HIP(c, hipMemcpyAsync(st, c->d_spread_cnt, SPREAD_CNT_BYTES, hipMemcpyDeviceToHost, c->prep_stream));
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  for (int32_t k = 0; k < count; ++k) st[keys[(size_t)k]] = value[k];
+  MSH_HIP(c, hipMemcpyAsync(c->d_spread_cnt, st, SPREAD_CNT_BYTES, hipMemcpyHostToDevice, c->prep_stream));
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+
+int msh_reset_spread_counts(msh_ctx* c) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->d_spread_cnt) return MSH_OK;  // never used: nothing to zero
+  DeviceGuard g(c->device);
+  int rc = after_seq(c);
+  if (rc != MSH_OK) return rc;
+  if ((rc = spread_zero_counts(c)) != MSH_OK) return rc;
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+
+int msh_seq_spread_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = msh::seq_spread_max_nodes(nres);
+  return MSH_OK;
+}
+
+namespace {
+// What a spread call needs, checked before any device work (`entry`: the name for messages).
+int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node) {
+  if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
+  if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
+  int rc = refuse_random(c, entry);
+  if (rc != MSH_OK) return rc;
+  if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
+  if (c->rs_mode != MSH_RESOURCE_SCORE_NONE)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                std::string(entry) + ": a resource score (msh_set_resource_score) together with topology spread is "
+                                     "not implemented (MSH_RESOURCE_SCORE_NONE restores the unscored form)");
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (!c->have_zone) return fail(c, MSH_ERR_STATE, "msh_upload_node_zones has not been called");
+  if (nres) {
+    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+    if (nres != c->nres)
+      return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
+                                          std::to_string(c->nres));
+  }
+  if (c->n_nodes > msh::seq_spread_max_nodes(nres))
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "the topology-spread form keeps the node state in registers: at most " +
+                    std::to_string(msh::seq_spread_max_nodes(nres)) + " nodes per device with " +
+                    std::to_string(nres) + (nres == 1 ? " resource" : " resources"));
+  return MSH_OK;
+}
+
+int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                  const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req, int32_t max_pods_per_node,
+                  int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status, void* stream) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_pod_group || !d_out_idx || !d_out_status))  // d_out_score optional
+    return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
+  int rc = spread_check(c, entry, p, nres, max_pods_per_node);
+  if (rc != MSH_OK) return rc;
+  if (p == 0) return MSH_OK;
+  DeviceGuard g(c->device);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  msh::SpreadArgs sa{};
+  msh::SeqArgs& a = sa.f.s;
+  a.planes = cur_table(c).d_planes;
+  a.n_words = c->n_pad / 32;
+  a.n_nodes = c->n_nodes;
+  a.pod_digit = d_pod_digit;
+  a.pod_tol = d_pod_tol;
+  a.n_pods = p;
+  a.pp = c->pp;
+  // the pod count limit as the resource-fit form takes it: the column and / or the scalar, or none
+  a.max_pods = max_pods_per_node == 0 ? INT32_MAX : max_pods_per_node;
+  a.cap = c->have_cap ? c->d_cap : nullptr;
+  a.counts = c->d_counts;
+  a.count_stride = (int64_t)c->counts_cap;
+  a.count_replicas = c->counts_replicas;
+  a.fold = c->counts_dirty ? 1 : 0;
+  a.out_idx = d_out_idx;
+  a.out_score = d_out_score;
+  a.out_status = d_out_status;
+  sa.f.nres = nres;
+  sa.f.res_stride = (int64_t)c->res_cap;
+  sa.f.alloc = nres ? c->d_alloc : nullptr;
+  sa.f.used = nres ? c->d_used : nullptr;
+  sa.f.pod_req = nres ? d_pod_req : nullptr;
+  sa.zone = c->d_zone;
+  sa.pod_group = d_pod_group;
+  sa.n_groups = c->sp_groups;
+  sa.max_skew = c->d_skew;
+  sa.cnt = c->d_spread_cnt;
+  sa.zset = c->zset;
+  // one sequential launch of a ctx at a time (seq_device): each commits into the same counts
+  for (auto& ev : c->seq_inflight)
+    if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
+  std::string err;
+  hipError_t e;
+  {
+    TimedLaunch tl(c);
+    e = msh::launch_seq_spread(sa, s, &err);
+  }
+  if (e != hipSuccess) {
+    if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
+    return hip_fail(c, e, "seq_spread_kernel");
+  }
+  c->counts_dirty = false;  // the one workgroup folded the replicas
+  return track_launch(c, s, true);
+}
+}  // namespace
+
+int msh_schedule_sequential_spread_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                          const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req,
+                                          int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
+                                          int32_t* d_out_status, void* stream) {
+  return spread_device(c, "msh_schedule_sequential_spread_device", p, d_pod_digit, d_pod_tol, d_pod_group, nres,
+                       d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+}
+
+int msh_schedule_sequential_spread(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                   const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
+                                   int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+                                   int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  const char* entry = "msh_schedule_sequential_spread";
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (p > 0 && (!pod_digit || !pod_tol || !pod_group || !out_idx || !out_status))  // out_score optional
+    return fail(c, MSH_ERR_INVALID, "null host pointer");
+  if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
+  int rc = spread_check(c, entry, p, nres, max_pods_per_node);
+  if (rc != MSH_OK) return rc;
+  for (int32_t j = 0; j < p; ++j)
+    if (pod_group[j] < -1 || pod_group[j] >= c->sp_groups)
+      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": group " + std::to_string(pod_group[j]) +
+                                          " outside [-1, G) with G = " + std::to_string(c->sp_groups));
+  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e)
+    if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
+      return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
+  if (p == 0) return MSH_OK;
+  DeviceGuard g(c->device);
+  HostIO io;
+  if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
+  // the requests and the groups through the page-locked node stage, which the kernel reads itself (free here:
+  // every writer that uses it has finished its copies, and this call ends only when the kernel has)
+  const size_t rbytes = (size_t)nres * (size_t)p * sizeof(int64_t);
+  if ((rc = node_stage(c, rbytes + (size_t)p * sizeof(int32_t))) != MSH_OK) return rc;
+  if (rbytes) std::memcpy(c->h_nstage, pod_req, rbytes);
+  std::memcpy(c->h_nstage + rbytes, pod_group, (size_t)p * sizeof(int32_t));
+  rc = spread_device(c, entry, p, io.d_pd, io.d_pt, reinterpret_cast<const int32_t*>(c->h_nstage + rbytes), nres,
+                     reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
+                     io.o_status, c->stream);
+  if (rc != MSH_OK) return rc;
+  if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
+  if (commit_cb)
+    for (int32_t j = 0; j < p; j++)
+      if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
   return MSH_OK;
 }
 

@@ -101,6 +101,20 @@ struct msh_ctx {
   int32_t rs_nres = 0;
   int32_t rs_w[MSH_MAX_RESOURCES] = {};
   int64_t res_max = 0;
+  // topology spread (msh_schedule_sequential_spread), unversioned like the counts. The zone column
+  // (msh_upload_node_zones): zone_cap int32 on the device (-1 in the padding slots), its host copy and Zset, the
+  // ids that occur on a node; dropped by msh_upload_nodes. The groups (msh_set_spread_groups): sp_groups of them
+  // with their max_skew on the host and in d_skew. The counts cnt[g][z], on the device only (every spread commit
+  // changes them): d_skew and d_spread_cnt are allocated whole (MSH_MAX_SPREAD_GROUPS rows) at first use.
+  int32_t* d_zone = nullptr;
+  size_t zone_cap = 0;
+  bool have_zone = false;
+  std::vector<int32_t> h_zone;
+  uint64_t zset = 0;
+  int32_t sp_groups = 0;
+  std::vector<int32_t> h_skew;
+  int32_t* d_skew = nullptr;
+  int32_t* d_spread_cnt = nullptr;
   // per caller stream, the event of its last sequential launch: an alias of a table version's reader
   // event (not owned here; track_launch)
   std::vector<std::pair<hipStream_t, hipEvent_t>> seq_inflight;

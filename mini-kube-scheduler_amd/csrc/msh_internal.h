@@ -300,6 +300,22 @@ struct FitScoreArgs {
 };
 int32_t seq_score_max_nodes(int32_t nres);
 hipError_t launch_seq_score(const FitScoreArgs& a, hipStream_t s, std::string* err);
+// The topology-spread form (msh_seq_spread.hip, msh_schedule_sequential_spread): the resource-fit loop with
+// upstream's PodTopologySpread filter. f.nres may be 0 (no table: alloc, used and pod_req are not read).
+constexpr int SPREAD_ZONES = 64;        // MSH_MAX_ZONES
+constexpr int SPREAD_MAX_GROUPS = 128;  // MSH_MAX_SPREAD_GROUPS
+struct SpreadArgs {
+  FitArgs f;
+  const int32_t* zone;       // [f.s.n_words * 32]: the node's zone id in [0, SPREAD_ZONES), -1 without one (padding too)
+  const int32_t* pod_group;  // [f.s.n_pods]: any value outside [0, n_groups) is an ungrouped pod
+  int32_t n_groups;          // 0..SPREAD_MAX_GROUPS
+  const int32_t* max_skew;   // [n_groups], each >= 1
+  int32_t* cnt;              // [n_groups][SPREAD_ZONES]: read at the start, written back at the end
+  uint64_t zset;             // bit z: zone z occurs on a node of the table
+};
+// Nodes the topology-spread kernel holds for a table of nres resources (0..FIT_MAX_RES): the resource-fit limits.
+int32_t seq_spread_max_nodes(int32_t nres);
+hipError_t launch_seq_spread(const SpreadArgs& a, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

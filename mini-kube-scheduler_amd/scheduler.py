@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _native as N
 from .framework import (NODE_NUMBER, NODE_UNSCHEDULABLE, SCORE_COLUMNS, Normalize, Outcome, ScheduleResult)
-from .snapshot import NodeTable, PodTable, node_allocatable, pack_nodes, pack_pods, pod_requests
+from .snapshot import NodeTable, PodTable, _get, node_allocatable, pack_nodes, pack_pods, pod_requests
 
 FILTER_IDS = {NODE_UNSCHEDULABLE: N.MSH_PLUGIN_NODE_UNSCHEDULABLE}
 SCORE_IDS = {NODE_NUMBER: N.MSH_PLUGIN_NODE_NUMBER,
@@ -417,6 +417,106 @@ class DeviceContext:
         self._check(self._lib.msh_seq_fit_max_nodes(self.handle, int(nres), 1 if scored else 0, C.byref(out)))
         return out.value
 
+    # -- pod topology spread for sequential mode (PodTopologySpread, DoNotSchedule: zones, groups, counts) --
+    @staticmethod
+    def _int32s(a, what: str) -> np.ndarray:
+        a = np.asarray(a)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError(f"{what}: a one-dimensional integer array")
+        if a.size and (int(a.min()) < -N.INT32_MAX - 1 or int(a.max()) > N.INT32_MAX):
+            raise ValueError(f"{what}: integers within int32")
+        return np.ascontiguousarray(a, np.int32)
+
+    def upload_node_zones(self, zone) -> None:
+        """msh_upload_node_zones: one zone id per uploaded node, List order, in [0, MAX_ZONES) or -1 for a node
+        without the topology key. Replaces the column and zeroes the spread counts. upload_nodes drops it;
+        patch_nodes, reset_node_pod_counts and the capacity and resource writers keep it."""
+        zone = self._int32s(zone, "zones")
+        self._check(self._lib.msh_upload_node_zones(self.handle, len(zone), N.ptr(zone)))
+
+    def clear_node_zones(self) -> None:
+        """msh_clear_node_zones: back to "no column"."""
+        self._check(self._lib.msh_clear_node_zones(self.handle))
+
+    def node_zones(self) -> np.ndarray | None:
+        """msh_node_zones: the column (int32, List order), or None when no column is present."""
+        present = C.c_int32(0)
+        out = np.zeros(self.n_nodes, np.int32)
+        self._check(self._lib.msh_node_zones(self.handle, N.ptr(out) if self.n_nodes else None, C.byref(present)))
+        return out if present.value else None
+
+    def set_spread_groups(self, max_skew) -> None:
+        """msh_set_spread_groups: one max_skew >= 1 per spread group, at most MAX_SPREAD_GROUPS of them (an empty
+        list: no groups). Another number of groups zeroes the spread counts; the same number only updates the skews."""
+        sk = self._int32s(max_skew, "max_skew")
+        self._check(self._lib.msh_set_spread_groups(self.handle, len(sk), N.ptr(sk) if len(sk) else None))
+
+    def spread_groups(self) -> np.ndarray:
+        """msh_get_spread_groups: the groups' max_skew (int32, one per group)."""
+        g = C.c_int32(0)
+        self._check(self._lib.msh_get_spread_groups(self.handle, C.byref(g), None))
+        out = np.zeros(g.value, np.int32)
+        self._check(self._lib.msh_get_spread_groups(self.handle, C.byref(g), N.ptr(out) if g.value else None))
+        return out
+
+    def spread_counts(self) -> np.ndarray:
+        """msh_spread_counts: cnt[g][z] shaped (G, MAX_ZONES), int32: the committed pods of group g in zone z."""
+        g = len(self.spread_groups())
+        out = np.zeros((g, N.MAX_ZONES), np.int32)
+        self._check(self._lib.msh_spread_counts(self.handle, N.ptr(out) if g else None))
+        return out
+
+    def patch_spread_counts(self, g, z, value) -> None:
+        """msh_patch_spread_counts: value[k] replaces cnt[g[k]][z[k]] (distinct pairs, values >= 0): accounts for a
+        deleted pod, or for pods bound elsewhere."""
+        g, z, value = (self._int32s(a, "spread count patch") for a in (g, z, value))
+        if not len(g) == len(z) == len(value):
+            raise ValueError("g / z / value length mismatch")
+        self._check(self._lib.msh_patch_spread_counts(self.handle, len(g), N.ptr(g), N.ptr(z), N.ptr(value)))
+
+    def reset_spread_counts(self) -> None:
+        """msh_reset_spread_counts: every spread count to 0."""
+        self._check(self._lib.msh_reset_spread_counts(self.handle))
+
+    def seq_spread_max_nodes(self, nres: int = 0) -> int:
+        """msh_seq_spread_max_nodes: the largest table schedule_sequential_spread takes with nres (0..4) resources."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_spread_max_nodes(self.handle, int(nres), C.byref(out)))
+        return out.value
+
+    def schedule_sequential_spread(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_group, pod_req=None,
+                                   max_pods_per_node: int = 0,
+                                   on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_spread: schedule_sequential_fit with a spread group per pod (-1: none). A pod of
+        group g is placed only on a node with a zone where cnt[g][zone] + 1 - min over the table's zones of cnt[g]
+        stays within max_skew[g]; a placement adds 1 to cnt[g][zone]. pod_req (nres, p) as in
+        schedule_sequential_fit, or None: no requests are checked or committed."""
+        pod_digit = np.ascontiguousarray(pod_digit, np.int8)
+        pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
+        pod_group = self._int32s(pod_group, "pod_group")
+        p = _same_len("schedule_sequential_spread", pod_digit, pod_tol, pod_group)
+        nres = 0
+        if pod_req is not None:
+            pod_req = self._amounts(pod_req)
+            if pod_req.shape[1] != p:
+                raise ValueError("pod_req is shaped (nres, p)")
+            nres = pod_req.shape[0]
+        idx, score, status = self._outputs(p, out)
+        cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
+        self._check(self._lib.msh_schedule_sequential_spread(
+            self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), nres,
+            N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
+        return idx, score, status
+
+    def schedule_sequential_spread_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int, nres: int,
+                                          d_pod_req: int, max_pods_per_node: int, d_idx: int, d_score: int,
+                                          d_status: int, stream: int = 0) -> None:
+        """msh_schedule_sequential_spread_device (asynchronous on `stream`; d_pod_req and d_pod_group are not
+        validated: a group outside [0, G) is an ungrouped pod)."""
+        self._check(self._lib.msh_schedule_sequential_spread_device(
+            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group, int(nres), d_pod_req or None,
+            int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):
     # ctypes argument conversion cost ~0.9 us per call next to a ~2.6 us launch.
@@ -615,6 +715,14 @@ class Scheduler:
     each feasible node to schedule_sequential's totals, at plugin weight resource_score_weight. resource_weights
     is a mapping from resource name to weight, or a sequence aligned with `resources` (default: 1 each; 0: fitted
     but not scored). It needs `resources`. The library substitutes no defaults for pods that request nothing.
+
+    zones and spread_groups (default None; given together) add upstream's PodTopologySpread filter (DoNotSchedule) to
+    schedule_sequential: `zones` names the node label that holds the topology domain (e.g.
+    "topology.kubernetes.io/zone"; at most 64 distinct values, a node without the label takes no grouped pod),
+    `spread_groups` maps a group name to its max_skew, and a pod belongs to the group named by its `spread_label`
+    label (default "app"), or to none. A grouped pod is placed only where its group's count in the node's zone stays
+    within max_skew of the group's emptiest zone (DeviceContext.schedule_sequential_spread); with `resources` the
+    requests are fitted too. Not available together with resource_score. schedule_batch ignores them.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
@@ -622,8 +730,22 @@ class Scheduler:
                  score_plugins: Sequence[ScorePluginConfig | str] = (NODE_NUMBER,),
                  device: int = 0, ctx: DeviceContext | None = None, *, tie_break="first", tie_seed: int = 0,
                  resources: Sequence[str] | None = None, resource_score=None, resource_score_weight: int = 1,
-                 resource_weights=None):
+                 resource_weights=None, zones: str | None = None, spread_groups: Mapping[str, int] | None = None,
+                 spread_label: str = "app"):
         self.resources = None if resources is None else tuple(resources)
+        if (zones is None) != (spread_groups is None):
+            raise ValueError("zones and spread_groups go together")
+        if spread_groups is not None:
+            if resource_score is not None:
+                raise ValueError("resource_score together with spread_groups is not implemented")
+            if len(spread_groups) > N.MAX_SPREAD_GROUPS:
+                raise ValueError(f"spread_groups: at most {N.MAX_SPREAD_GROUPS} groups")
+            if any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= N.INT32_MAX for v in spread_groups.values()):
+                raise ValueError("spread_groups: each max_skew an integer in [1, INT32_MAX]")
+        self.zones = zones
+        self.spread_label = spread_label
+        self.spread_groups = None if spread_groups is None else dict(spread_groups)
+        self._group_ids = {} if spread_groups is None else {name: k for k, name in enumerate(self.spread_groups)}
         if self.resources is not None and not 1 <= len(self.resources) <= N.MAX_RESOURCES:
             raise ValueError(f"resources: 1 to {N.MAX_RESOURCES} names")
         rs_weights = self._resource_weights(self.resources, resource_score, resource_weights)
@@ -639,6 +761,9 @@ class Scheduler:
             self.ctx.set_tiebreak(tie_break, tie_seed)
         if rs_weights is not None:
             self.ctx.set_resource_score(resource_score, resource_score_weight, rs_weights)
+        if self.spread_groups is not None:
+            self.ctx.set_spread_groups(list(self.spread_groups.values()))
+        self._zone_synced = False  # the snapshot's zone column is on the device
         self.nodes: NodeTable | None = None
         self._cap_synced = False  # the snapshot's capacity column is on the device
         self._res_synced = False  # the snapshot's allocatable amounts are on the device
@@ -676,13 +801,14 @@ class Scheduler:
 
     # Replaces the per-cycle Nodes().List (minisched.go:40) with one device upload.
     def update_nodes(self, nodes: Iterable[Any]) -> NodeTable:
-        if self.resources is not None:
+        if self.resources is not None or self.zones is not None:
             nodes = list(nodes)
         self.nodes = pack_nodes(nodes)
         self.ctx.upload_nodes(self.nodes.unsched, self.nodes.digit)  # drops the device's capacity column and resources
         self._cap_synced = False
         self._res_synced = False
-        if self.resources is not None:
+        self._zone_synced = False
+        if self.resources is not None or self.zones is not None:
             self._node_objs = [nodes[i] for i in self.nodes.order]
         return self.nodes
 
@@ -722,15 +848,17 @@ class Scheduler:
             self.update_nodes(nodes)
         if self.nodes is None:
             raise N.MshError(N.MSH_ERR_STATE, "no node snapshot: call update_nodes() first")
-        if self.resources is not None:
+        if self.resources is not None or self.zones is not None:
             pods = list(pods)
         table = pack_pods(pods)
         if self.nodes.allocatable_pods is not None and not self._cap_synced:
             self.ctx.upload_node_capacity(self.nodes.allocatable_pods)
             self._cap_synced = True
-        if self.resources is None:
+        if self.resources is None and self.zones is None:
             idx, score, status = self.ctx.schedule_sequential(table.digit, table.tolerates, max_pods_per_node)
             return self._results(table, idx, score, status)
+        if self.zones is not None:
+            return self._schedule_spread(pods, table, max_pods_per_node)
         if not self._res_synced:
             alloc = np.array([node_allocatable(n, self.resources) for n in self._node_objs], np.int64)
             self.ctx.upload_node_resources(alloc.reshape(len(self._node_objs), len(self.resources)).T)
@@ -738,4 +866,38 @@ class Scheduler:
         req = np.array([pod_requests(p, self.resources) for p in pods], np.int64)
         req = req.reshape(len(pods), len(self.resources)).T
         idx, score, status = self.ctx.schedule_sequential_fit(table.digit, table.tolerates, req, max_pods_per_node)
+        return self._results(table, idx, score, status)
+
+    def node_zone_ids(self) -> tuple[np.ndarray, list[str]]:
+        """The snapshot's zone column (List order; -1: the node lacks the `zones` label) and the zone names by id,
+        numbered in the order in which List order first shows them."""
+        names: dict[str, int] = {}
+        col = np.full(len(self._node_objs), -1, np.int32)
+        for i, n in enumerate(self._node_objs):
+            v = _get(n, "metadata", "labels", self.zones)
+            if v is not None:
+                col[i] = names.setdefault(str(v), len(names))
+        if len(names) > N.MAX_ZONES:
+            raise ValueError(f"{len(names)} distinct values of {self.zones!r}: at most {N.MAX_ZONES} zones")
+        return col, list(names)
+
+    def pod_group_ids(self, pods: Sequence[Any]) -> np.ndarray:
+        """A pod's spread group: the index in spread_groups of its `spread_label` label's value, else -1."""
+        labels = [_get(p, "metadata", "labels", self.spread_label) for p in pods]
+        return np.array([-1 if v is None else self._group_ids.get(str(v), -1) for v in labels], np.int32).reshape(len(pods))
+
+    def _schedule_spread(self, pods, table, max_pods_per_node: int) -> list[ScheduleResult]:
+        if not self._zone_synced:
+            self.ctx.upload_node_zones(self.node_zone_ids()[0])
+            self._zone_synced = True
+        req = None
+        if self.resources is not None:
+            if not self._res_synced:
+                alloc = np.array([node_allocatable(n, self.resources) for n in self._node_objs], np.int64)
+                self.ctx.upload_node_resources(alloc.reshape(len(self._node_objs), len(self.resources)).T)
+                self._res_synced = True
+            req = np.array([pod_requests(p, self.resources) for p in pods], np.int64)
+            req = req.reshape(len(pods), len(self.resources)).T
+        idx, score, status = self.ctx.schedule_sequential_spread(table.digit, table.tolerates, self.pod_group_ids(pods),
+                                                                 req, max_pods_per_node)
         return self._results(table, idx, score, status)
