@@ -131,7 +131,8 @@ typedef struct msh_options {
   int32_t struct_size;  /* sizeof(msh_options) */
   int32_t batch_kernel; /* 0 auto | 1 generic_kernel (explicit int64 score per pair) for every plugin list */
   int32_t pair_planes;  /* 0 auto | 1 node planes by scalar loads | 2 staged in LDS (tables that fit) */
-  int32_t pair_noax;    /* 0 auto | 1 LDS form: group 0 first, settled reductions dropped | 2 group 0 last */
+  int32_t pair_noax;    /* 0 auto | 1 LDS form: group 0 first, settled reductions dropped | 2 group 0 last
+                         * (REVERSE / MINMAX; NONE / DEFAULT have no such reduction: accepted, no effect) */
   int32_t pair_slices;  /* 0 auto | 1, 2, 4 slice waves per 64-pod block (and generic_kernel pod group) */
   int32_t seq_waves;    /* 0 auto | 1, 4, 15, 16 scanning waves of the sequential kernel (raised when too few) */
   int32_t seq_split;    /* 0 auto (no capacity: the batch kernel + counts) | 1 one workgroup walks the

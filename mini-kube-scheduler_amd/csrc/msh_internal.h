@@ -48,7 +48,9 @@ struct DeviceInfo {
   // reduction from the scan of the other groups when group 0 has settled it for every lane of the
   // wave (1), or scans group 0 last and never drops it (0). -1 = auto: 1 for REVERSE / MINMAX (78.1
   // against 89.0 us per 32-batch C3 launch), 0 for the identity-like modes (77.3-78.3 against
-  // 80.9-81.2), profiles/r4_ab_pair_planes.txt
+  // 80.9-81.2), profiles/r4_ab_pair_planes.txt. The identity-like modes no longer carry a feasible
+  // reduction in the LDS form (the first feasible node comes from the scalar unit): the option is still
+  // accepted and has no effect on them
   int pair_noax = -1;
   // msh_options.seq_split, without a capacity: the per-pair batch kernel with the commit epilogue (auto,
   // 2), the sequential kernel's 64-pod blocks of consecutive pods, one workgroup each (1), or the whole

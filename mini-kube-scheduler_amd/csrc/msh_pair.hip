@@ -28,6 +28,15 @@ __device__ __forceinline__ void sload_group(u32x8* pl, const uint32_t* src) {
                  "+s"(pl[5]));
 }
 
+// The X and V planes of one group (grp: its first dword) into pl[PLANE_X] and pl[PLANE_V], the two that
+// group_feasible_s and group_first_feasible_s read; the code planes of pl are left unset. Same idiom
+// as sload_group: the wait is part of the asm block that defines the registers.
+__device__ __forceinline__ void sload_xv(u32x8 (&pl)[PLANE_N], const uint32_t* grp) {
+  asm volatile("s_load_dwordx8 %0, %2, %3\n\ts_load_dwordx8 %1, %2, %4\n\ts_waitcnt lgkmcnt(0)"
+               : "=&s"(pl[PLANE_X]), "=&s"(pl[PLANE_V])
+               : "s"(grp), "n"(PLANE_X * PLANE_GW * 4), "n"(PLANE_V * PLANE_GW * 4));
+}
+
 // NPL planes of group g: by scalar loads (LDSP false), or (LDSP) from the workgroup's LDS copy of the
 // table as wave-uniform ds_read_b128 (a broadcast) into VGPRs.
 template <int NPL, bool LDSP>
@@ -345,8 +354,11 @@ __global__ __launch_bounds__(PAIR_WAVES * WAVE) void pair_kernel(PairArgsN<NB> a
 // Each wave evaluates PL_BPW = 2 64-pod blocks together: a group's planes are read from LDS once per
 // wave and applied to both, and the table copy is amortised over W x 2 blocks.
 // Per lane and 32-node word: xi = X & nT, dm' (4 v_bitop3), and per two words one AND3 into the
-// group's match flag, plus, KX, one OR of the feasible non-matches (dm' & ~xi), or, identity-like
-// modes, one AND3 of two words' xi per two words (the group holds a feasible node iff not all-ones).
+// group's match flag, plus, KX, one OR of the feasible non-matches (dm' & ~xi): 5.5 VALU per word in
+// the identity-like modes, 6.5 with KX. The identity-like modes need no per-lane reduction beside the
+// match flag: a pod without a feasible match takes its first feasible node, which depends on the pod
+// only through its tolerates bit, so the wave computes the two answers on the scalar unit as
+// pair_kernel does (fn / ft during the scan, group_first_feasible_s after it) and a lane selects one.
 // The forms that lost their A/B (profiles/r4_ab_pair_planes.txt) are no longer built:
 // one, three and four blocks per wave; the pure-LDS full-group form (a full group always takes hybrid
 // planes: X and D3 by scalar loads, D0-D2 from LDS); compaction in the identity-like modes and hybrid
@@ -381,8 +393,8 @@ __device__ __forceinline__ uint32_t pair_miss_v(const uint32_t (&pl)[PLANE_N][PL
   return bop3_or_xor(t, pl[3][w], P3);
 }
 
-// One group: am &= its dm' words; KX: ax |= its feasible non-matches; else af &= its xi words (not
-// all-ones iff the group holds a node feasible for the pod; a padding group also ORs ~V into xi).
+// One group, all planes from LDS (REVERSE / MINMAX, a group holding padding): am &= its dm' words;
+// KX: ax |= its feasible non-matches.
 template <bool PAD, bool KX>
 __device__ __forceinline__ void pair_group_v(const uint32_t (&pl)[PLANE_N][PLANE_GW], uint32_t P0, uint32_t P1,
                                              uint32_t P2, uint32_t P3, uint32_t nT, uint32_t& am, uint32_t& ax) {
@@ -400,11 +412,6 @@ __device__ __forceinline__ void pair_group_v(const uint32_t (&pl)[PLANE_N][PLANE
         ax = bop3_or_andn(ax, t0, x0);
         ax = bop3_or_andn(ax, t1, x1);
       }
-    } else {
-      if constexpr (PAD) {  // infeasible: xi or not a real node
-        ax = bop3_and3(ax, x0 | ~pl[PLANE_V][w], x1 | ~pl[PLANE_V][w + 1]);
-      }
-      // (a group without padding: the caller folds nT & AND(X) into ax once per group)
     }
   }
 }
@@ -436,16 +443,16 @@ __device__ __forceinline__ void pair_group_ty(const uint32_t (&pl)[PLANE_N][PLAN
         else ax = PAD ? (ax | (t[h] & pl[PLANE_V][ww])) : (ax | t[h]);
       }
     }
-    if constexpr (!KX && PAD) {  // infeasible: X (TY 0) or not a real node
-      if constexpr (TY == 0) ax = bop3_and3(ax, pl[PLANE_X][w] | ~pl[PLANE_V][w], pl[PLANE_X][w + 1] | ~pl[PLANE_V][w + 1]);
-      else ax = bop3_and3(ax, ~pl[PLANE_V][w], ~pl[PLANE_V][w + 1]);
-    }
   }
 }
 
-// A full group (no padding slot) with planes 0-2 from LDS (VGPRs) and X, D3 by scalar loads (SGPRs):
-// 6 LDS reads per group instead of 10, at the price of two SGPR-operand v_bitop3 per word (the
-// "hybrid" form, MSH_PAIR_HYBRID). TY as pair_group_ty (2: mixed tolerates, X & nT per word).
+// A group with planes 0-2 from LDS (VGPRs) and X, D3 by scalar loads (SGPRs): 6 LDS reads per group
+// instead of 10, at the price of two SGPR-operand v_bitop3 per word (the "hybrid" form,
+// MSH_PAIR_HYBRID). TY as pair_group_ty (2: mixed tolerates, X & nT per word). KX: a full group only
+// (ax takes no V). Without KX any group: the match flag reads no V, because a padding slot carries
+// node code 15 in D0-D3 (msh_prep.hip node_prep_kernel and table_copy_kernel write CODE_NONE_NODE
+// there, and X = 0, V = 0), which differs from every pod code (0-9, 14) in some bit, so its dm' bit
+// is set through the code compare whatever X holds.
 template <bool KX, int TY>
 __device__ __forceinline__ void pair_group_hy(const uint32_t (&pl)[PLANE_N][PLANE_GW], const u32x8& X,
                                               const u32x8& D3, uint32_t P0, uint32_t P1, uint32_t P2, uint32_t P3,
@@ -481,18 +488,8 @@ __device__ __forceinline__ void pair_group_hy(const uint32_t (&pl)[PLANE_N][PLAN
   }
 }
 
-// The lane's first feasible node in group g (identity-like modes), NOFIT if none.
-__device__ __forceinline__ uint32_t group_first_feasible_v(const uint32_t (&pl)[PLANE_N][PLANE_GW], uint32_t g,
-                                                           uint32_t nT) {
-  uint32_t h[PLANE_GW];
-#pragma unroll
-  for (int c = 0; c < PLANE_GW; ++c) h[c] = pl[PLANE_V][c] & ~(pl[PLANE_X][c] & nT);
-  const uint32_t m = hits_first(h, 0u);
-  return m < GROUP_NODES ? g * GROUP_NODES + m : NOFIT;
-}
-
-// The lane's first feasible match (KIND 0), feasible non-match (1) or feasible node (2) in group g
-// of the LDS table, NOFIT if none: half a group (four words, 6 x 4 plane words live) at a time.
+// The lane's first feasible match (KIND 0) or feasible non-match (1) in group g of the LDS table,
+// NOFIT if none: half a group (four words, 6 x 4 plane words live) at a time.
 template <int KIND>
 __device__ __forceinline__ uint32_t group_first_lds(const uint4* __restrict__ s_tab, uint32_t g, uint32_t P0,
                                                     uint32_t P1, uint32_t P2, uint32_t P3, uint32_t nT) {
@@ -509,13 +506,8 @@ __device__ __forceinline__ uint32_t group_first_lds(const uint4* __restrict__ s_
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const uint32_t fe = ~(pl[PLANE_X][c] & nT) & pl[PLANE_V][c];
-      uint32_t h;
-      if constexpr (KIND == 2) {
-        h = fe;
-      } else {
-        const uint32_t dm = (pl[0][c] ^ P0) | (pl[1][c] ^ P1) | (pl[2][c] ^ P2) | (pl[3][c] ^ P3);
-        h = KIND == 1 ? (dm & fe) : (~dm & fe);
-      }
+      const uint32_t dm = (pl[0][c] ^ P0) | (pl[1][c] ^ P1) | (pl[2][c] ^ P2) | (pl[3][c] ^ P3);
+      const uint32_t h = KIND == 1 ? (dm & fe) : (~dm & fe);
       t[c] = lowbit(h) | (uint32_t)(32 * c);  // all-ones when the word has none
     }
     const uint32_t m = umin(umin(t[0], t[1]), umin(t[2], t[3]));
@@ -524,9 +516,10 @@ __device__ __forceinline__ uint32_t group_first_lds(const uint4* __restrict__ s_
   return NOFIT;
 }
 
-// Both firsts of group g in one pass over its planes (half a group at a time, the upper half only
-// when some lane needs it): the first feasible match (rm) and, KX, the first feasible non-match or,
-// else, the first feasible node (rx); NOFIT where the group has none. Called by whole waves.
+// The firsts of group g in one pass over its planes (half a group at a time, the upper half only
+// when some lane needs it): the first feasible match (rm) and, KX, the first feasible non-match (rx;
+// without KX it is left alone: the caller takes the first feasible node from the scalar unit); NOFIT
+// where the group has none. Called by whole waves.
 template <bool KX>
 __device__ __forceinline__ void group_firsts_lds(const uint4* __restrict__ s_tab, uint32_t g, uint32_t P0,
                                                  uint32_t P1, uint32_t P2, uint32_t P3, uint32_t nT, bool digit,
@@ -547,15 +540,15 @@ __device__ __forceinline__ void group_firsts_lds(const uint4* __restrict__ s_tab
       const uint32_t dm = (pl[0][c] ^ P0) | (pl[1][c] ^ P1) | (pl[2][c] ^ P2) | (pl[3][c] ^ P3);
       const uint32_t off = (uint32_t)(32 * (c + 4 * hh));
       bm = umin(bm, lowbit(~dm & fe) | off);  // all-ones stays all-ones for a word without one
-      bx = umin(bx, lowbit(KX ? (dm & fe) : fe) | off);
+      if constexpr (KX) bx = umin(bx, lowbit(dm & fe) | off);
     }
     // the upper half only when some lane's first match (a pod without a digit has none: its code
-    // matches no node's) or first feasible (non-match) is not in the lower one: with random digits
+    // matches no node's) or, KX, first feasible non-match is not in the lower one: with random digits
     // almost never, and the scan of group 0 halves
-    if (hh == 0 && __ballot((digit && bm == 0xFFFFFFFFu) || bx == 0xFFFFFFFFu) == 0) break;
+    if (hh == 0 && __ballot((digit && bm == 0xFFFFFFFFu) || (KX && bx == 0xFFFFFFFFu)) == 0) break;
   }
   rm = bm < GROUP_NODES ? g * GROUP_NODES + bm : NOFIT;
-  rx = bx < GROUP_NODES ? g * GROUP_NODES + bx : NOFIT;
+  if constexpr (KX) rx = bx < GROUP_NODES ? g * GROUP_NODES + bx : NOFIT;
 }
 
 // W waves per workgroup (PL_WAVES or PL_WAVES_BIG). REVERSE / MINMAX (KX) compact the tolerates bit in
@@ -661,18 +654,25 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
   if (!any_act) return;  // wave-uniform; no barrier below
   // Groups above 0, descending, two per step (as pair_kernel): each group's 40 / 48 plane words read
   // into VGPRs at once and applied to every block. fm / fx: the lower group of the lowest pair with a
-  // feasible match / KX: feasible non-match, identity-like: feasible node. (Reading half a group at a
-  // time, one group per iteration, cut the kernel to 52 VGPRs and 8 waves per SIMD but ran slower:
-  // 95.6 against 89.8 us per 32-batch C3 launch, profiles/r4_ab_pair_planes.txt.)
+  // feasible match / KX: feasible non-match. (Reading half a group at a time, one group per iteration,
+  // cut the kernel to 52 VGPRs and 8 waves per SIMD but ran slower: 95.6 against 89.8 us per 32-batch
+  // C3 launch, profiles/r4_ab_pair_planes.txt.)
+  // Identity-like modes: fn / ft, the lowest group above 0 with a node feasible for a pod that does
+  // not tolerate / that tolerates the taint. Wave-uniform, kept on the scalar unit, exact per group
+  // (not per pair of groups): a full group holds one for a non-tolerating pod iff AND(X) is not
+  // all-ones, and always one for a tolerating pod; a group with padding takes group_feasible_s<true>
+  // on its X and V planes. The scan has one body: a padded group takes hybrid planes too (its match
+  // flag reads no V, see pair_group_hy).
   uint32_t fm[PL_BPW], fx[PL_BPW];
 #pragma unroll
   for (int b = 0; b < PL_BPW; ++b) fm[b] = fx[b] = NO_GROUP;
-  // Group 0 first: every block's first hits in it (half-group reads; the upper half only when some
-  // lane needs it). When every lane already has its first feasible non-match (KX) or first feasible
-  // node there, the scan of the groups above needs only the match flags: every pair is still
-  // evaluated (dm' per word), but the non-match / feasible reduction, whose answer group 0 has
-  // settled, is left out (KX: 5.5 instead of 6.5 VALU per word).
-  constexpr int KIND_X = KX ? 1 : 2;  // KX: first feasible non-match; else first feasible node
+  uint32_t fn = NO_GROUP, ft = NO_GROUP;
+  // KX, group 0 first: every block's first hits in it (half-group reads; the upper half only when
+  // some lane needs it). When every lane already has its first feasible non-match there, the scan of
+  // the groups above needs only the match flags: every pair is still evaluated (dm' per word), but
+  // the non-match reduction, whose answer group 0 has settled, is left out (5.5 instead of 6.5 VALU
+  // per word). The identity-like modes have no such reduction, so msh_options.pair_noax does not
+  // bear on them: they scan group 0 last, for the first feasible match only.
   uint32_t rm[PL_BPW], rx[PL_BPW];
   auto group0 = [&]() {
 #pragma unroll
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
 #pragma unroll
       for (int b = 0; b < PL_BPW; ++b) {
         am[b] = 0xFFFFFFFFu;
-        ax[b] = KX ? 0u : 0xFFFFFFFFu;
+        ax[b] = 0u;
       }
       const int32_t g2 = g - 1 > 0 ? g - 1 : g;
       u32x8 spp[2][2];  // HY 2: X, D3 of both groups of the step, one wait for the four scalar loads
@@ -702,7 +702,7 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
         const int32_t gg = h == 0 ? g : g - 1;
         if (h == 1 && gg <= 0) break;
         uint32_t pl[PLANE_N][PLANE_GW];
-        if (gg < g_full) {  // a full group: hybrid planes
+        if (!KX || gg < g_full) {  // hybrid planes: a full group, or, identity-like modes, any group
           u32x8 sp[2];  // X, D3
           if constexpr (HY == 2) {
             sp[0] = spp[h][0];
@@ -719,10 +719,19 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
             else if (ty[b] == 1) pair_group_hy<KXS, 1>(pl, sp[0], sp[1], P0[b], P1[b], P2[b], P3[b], nT[b], am[b], ax[b]);
             else pair_group_hy<KXS, 2>(pl, sp[0], sp[1], P0[b], P1[b], P2[b], P3[b], nT[b], am[b], ax[b]);
           }
-          if constexpr (!KX && !NOAX) {  // nT & AND(X): the AND on the scalar unit
-            const uint32_t axg = sp[0][0] & sp[0][1] & sp[0][2] & sp[0][3] & sp[0][4] & sp[0][5] & sp[0][6] & sp[0][7];
-#pragma unroll
-            for (int b = 0; b < PL_BPW; ++b) ax[b] = bop3_and3(ax[b], nT[b], axg);
+          if constexpr (!KX) {  // fn / ft on the scalar unit
+            if (gg < g_full) {
+              const uint32_t axg = sp[0][0] & sp[0][1] & sp[0][2] & sp[0][3] & sp[0][4] & sp[0][5] & sp[0][6] & sp[0][7];
+              fn = axg != 0xFFFFFFFFu ? (uint32_t)gg : fn;
+              ft = (uint32_t)gg;
+            } else {
+              u32x8 xv[PLANE_N];
+              bool sn, st;
+              sload_xv(xv, a.planes + (size_t)gg * GROUP_DWORDS);
+              group_feasible_s<true>(xv, sn, st);
+              fn = sn ? (uint32_t)gg : fn;
+              ft = st ? (uint32_t)gg : ft;
+            }
           }
         } else {
           lds_group<PLANE_N>(pl, s_tab, gg);
@@ -737,11 +746,30 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
 #pragma unroll
       for (int b = 0; b < PL_BPW; ++b) {
         fm[b] = am[b] != 0xFFFFFFFFu ? (uint32_t)g2 : fm[b];
-        if constexpr (!NOAX) fx[b] = (KX ? ax[b] != 0u : ax[b] != 0xFFFFFFFFu) ? (uint32_t)g2 : fx[b];
+        if constexpr (KXS) fx[b] = ax[b] != 0u ? (uint32_t)g2 : fx[b];
       }
     }
   };
-  if (a.noax) {
+  if constexpr (!KX) {
+    scan(std::false_type{});
+    group0();
+    // The first feasible node for each tolerates value, exact, on the scalar unit (as pair_kernel):
+    // in group 0, else in fn / ft; then one select per lane and block.
+    u32x8 xv[PLANE_N];
+    sload_xv(xv, a.planes);
+    uint32_t an = group_first_feasible_s<true>(xv, 0u);
+    uint32_t at = group_first_feasible_s<false>(xv, 0u);
+    if (an == NOFIT && fn != NO_GROUP) {
+      sload_xv(xv, a.planes + (size_t)fn * GROUP_DWORDS);
+      an = group_first_feasible_s<true>(xv, fn);
+    }
+    if (at == NOFIT && ft != NO_GROUP) {
+      sload_xv(xv, a.planes + (size_t)ft * GROUP_DWORDS);
+      at = group_first_feasible_s<false>(xv, ft);
+    }
+#pragma unroll
+    for (int b = 0; b < PL_BPW; ++b) rx[b] = nT[b] ? an : at;
+  } else if (a.noax) {
     group0();
     bool xdone = true;
 #pragma unroll
@@ -761,9 +789,11 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
       rm[b] = group_first_lds<0>(s_tab, fm[b], P0[b], P1[b], P2[b], P3[b], nT[b]);
       if (rm[b] == NOFIT) rm[b] = group_first_lds<0>(s_tab, fm[b] + 1, P0[b], P1[b], P2[b], P3[b], nT[b]);
     }
-    if (rx[b] == NOFIT && fx[b] != NO_GROUP) {
-      rx[b] = group_first_lds<KIND_X>(s_tab, fx[b], P0[b], P1[b], P2[b], P3[b], nT[b]);
-      if (rx[b] == NOFIT) rx[b] = group_first_lds<KIND_X>(s_tab, fx[b] + 1, P0[b], P1[b], P2[b], P3[b], nT[b]);
+    if constexpr (KX) {
+      if (rx[b] == NOFIT && fx[b] != NO_GROUP) {
+        rx[b] = group_first_lds<1>(s_tab, fx[b], P0[b], P1[b], P2[b], P3[b], nT[b]);
+        if (rx[b] == NOFIT) rx[b] = group_first_lds<1>(s_tab, fx[b] + 1, P0[b], P1[b], P2[b], P3[b], nT[b]);
+      }
     }
     if (j < np) {
       if constexpr (SHARD) {
@@ -843,7 +873,8 @@ hipError_t launch_pair_t(PairArgs& a, const DeviceInfo& dev, hipStream_t s) {
   // (big: two 16-wave workgroups per CU fill it from 32 blocks per CU on; 4-wave workgroups from 64 waves
   // per CU)
   const int64_t min_waves = (int64_t)dev.cus * (big ? 2 * PL_WAVES_BIG : 64);
-  // (counting launches, sequential mode: always scalar-loaded planes, whose kernel has the commit epilogue)
+  // (counting launches, sequential mode: always pair_kernel, which has the commit epilogue; launch_pair_s
+  // stages its planes in LDS too when the table fits)
   const bool lds = !a.counts && (fits || big) && (dev.pair_planes == 2 ||
                                      (dev.pair_planes == 0 && waves >= min_waves && dev.bits_slices == 0));
   if (lds) {
