@@ -42,7 +42,7 @@ SOURCES = [
     ("msh_pack.cpp", "g++", []),
 ]
 HEADERS = [CSRC / "msh_internal.h", CSRC / "msh_device.h", CSRC / "msh_pool.h", CSRC / "msh_ctx.h", CSRC / "msh_seq_kernel.h",
-           INCLUDE / "minisched_hip.h"]
+           CSRC / "msh_seq_frame.h", INCLUDE / "minisched_hip.h"]
 
 
 def _hipcc() -> str:

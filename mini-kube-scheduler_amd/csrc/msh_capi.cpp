@@ -1198,9 +1198,7 @@ int fit_check(msh_ctx* c, int32_t nres) {
                                         " resources, the table has " + std::to_string(c->nres));
     if (c->n_nodes > msh::seq_score_max_nodes(nres))
       return fail(c, MSH_ERR_UNSUPPORTED,
-                  "the scored resource-fit form keeps the node state in registers: at most " +
-                      std::to_string(msh::seq_score_max_nodes(nres)) + " nodes per device with " +
-                      std::to_string(nres) + (nres == 1 ? " resource" : " resources"));
+                  msh::seq_table_limit_message("scored resource-fit", msh::seq_score_max_nodes(nres), nres));
     if (c->res_max > MSH_RESOURCE_SCORE_MAX)
       return fail(c, MSH_ERR_UNSUPPORTED,
                   "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
@@ -1209,9 +1207,7 @@ int fit_check(msh_ctx* c, int32_t nres) {
   }
   if (c->n_nodes > msh::seq_fit_max_nodes(nres))
     return fail(c, MSH_ERR_UNSUPPORTED,
-                "the resource-fit form keeps the node state in registers: at most " +
-                    std::to_string(msh::seq_fit_max_nodes(nres)) + " nodes per device with " + std::to_string(nres) +
-                    (nres == 1 ? " resource" : " resources"));
+                msh::seq_table_limit_message("resource-fit", msh::seq_fit_max_nodes(nres), nres));
   return MSH_OK;
 }
 
@@ -1883,9 +1879,7 @@ int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t
   }
   if (c->n_nodes > msh::seq_spread_max_nodes(nres))
     return fail(c, MSH_ERR_UNSUPPORTED,
-                "the topology-spread form keeps the node state in registers: at most " +
-                    std::to_string(msh::seq_spread_max_nodes(nres)) + " nodes per device with " +
-                    std::to_string(nres) + (nres == 1 ? " resource" : " resources"));
+                msh::seq_table_limit_message("topology-spread", msh::seq_spread_max_nodes(nres), nres));
   return MSH_OK;
 }
 

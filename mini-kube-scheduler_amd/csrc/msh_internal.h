@@ -287,6 +287,12 @@ struct FitArgs {
   int64_t* used;           // [nres][res_stride]: read at the start, written back at the end
   const int64_t* pod_req;  // [nres][s.n_pods]
 };
+// What a call past a register-resident form's table limit is refused with (the launchers and the host checks):
+// form is "resource-fit", "scored resource-fit" or "topology-spread", limit its seq_*_max_nodes(nres).
+inline std::string seq_table_limit_message(const char* form, int32_t limit, int32_t nres) {
+  return std::string("the ") + form + " form keeps the node state in registers: at most " + std::to_string(limit) +
+         " nodes per device with " + std::to_string(nres) + (nres == 1 ? " resource" : " resources");
+}
 // Nodes the resource-fit kernel holds for a table of nres resources (8,192 up to two, 4,096 for three or four).
 int32_t seq_fit_max_nodes(int32_t nres);
 hipError_t launch_seq_fit(const FitArgs& a, hipStream_t s, std::string* err);

@@ -1,9 +1,14 @@
 // msh_seq_spread.hip — the topology-spread form of the sequential-commit kernel (msh_schedule_sequential_spread):
-// seq_fit_kernel's frame (msh_seq_fit.hip: thread t holds NPL consecutive nodes with their free amounts, remaining
+// seq_fit_kernel's frame (msh_seq_frame.h: thread t holds NPL consecutive nodes with their free amounts, remaining
 // pod count, codes and availability bits; pods arrive by readlane from the 64-pod block the lanes loaded; one
 // LDS-only barrier per pod with more than one wave) with upstream's PodTopologySpread filter (DoNotSchedule) as
 // one more conjunct. It is the first conjunct here that one commit changes for many nodes at once: every node of
 // the chosen zone and, through the minimum, every node of every zone.
+// The kernel body is still a copy of the frame, not a policy on it. Written as FirstFeasible with the conjunct as
+// hooks it gave the same results, but the compiler then dropped the branch that lets a wave none of whose lanes
+// holds a candidate node skip that node's compares, and the C5 launches ran 2.2-3.1% slower (151.9 against 147.3 ms
+// ungrouped, 170.6 against 166.9 ms grouped, profiles/seq_frame_refactor.json). The reduction, the launcher ladder
+// and the table-limit message are the frame header's.
 //  * zone ids: each thread packs the zone ids of its NPL nodes into one 64-bit register pair, 8 bits per node,
 //    and keeps one bit per node for "has a zone" (hz). A node without a zone holds id 0 and a clear hz bit; a
 //    grouped pod's availability bits are ANDed with hz, so such a node never tests as allowed, whatever the mask.
@@ -11,7 +16,7 @@
 //    loads them, the epilogue writes cnt back.
 //  * per grouped pod (g wave-uniform, from the lanes that loaded the block; any value outside [0, G) was turned
 //    into -1 there, so LDS is never indexed with it): lane z reads cnt[g][z]; lanes outside Zset contribute
-//    INT32_MAX to a wave minimum (DPP, as seq_score_kernel's maximum); allowed = ballot(z in Zset && cnt - minc <=
+//    INT32_MAX to a wave minimum (wave_reduce); allowed = ballot(z in Zset && cnt - minc <=
 //    max_skew - 1) is one 64-bit wave-uniform mask, and per node the extra conjunct is (allowed >> zone) & 1. No
 //    per-lane gather of cnt[g][zone(node)]. An ungrouped pod takes allowed = ~0 and every hz bit set.
 //  * the commit: the thread that holds the selected node knows its zone and adds 1 to cnt[g][zone].
@@ -23,23 +28,9 @@
 // and no barrier is needed.
 // Table limits and instances are seq_fit_kernel's: NPL = 8 for up to two resources (8,192 nodes), 4 for three or
 // four (4,096); a table of no, one or three resources runs the next larger instance with zero requests.
-#include "msh_seq_kernel.h"
+#include "msh_seq_frame.h"
 
 namespace msh {
-
-namespace {
-// The wave's minimum (signed, every lane active), wave-uniform: four DPP steps leave every row of 16 lanes with
-// its minimum, the four rows meet on the scalar side (seq_score_kernel's wave_umax, for a minimum).
-__device__ __forceinline__ int32_t wave_imin(int32_t v) {
-  v = min(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-  v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-  v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false));  // row_mirror
-  const int32_t a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-  const int32_t c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-  return min(min(a, b), min(c, d));
-}
-}  // namespace
 
 template <int NR, int NPL, int NW, bool KX>
 __global__ __launch_bounds__(NW * WAVE) void seq_spread_kernel(SpreadArgs sa) {
@@ -158,7 +149,7 @@ __global__ __launch_bounds__(NW * WAVE) void seq_spread_kernel(SpreadArgs sa) {
       if (pg >= 0) {  // wave-uniform
         const int32_t c = lcnt[pg * SPREAD_ZONES + lane];
         const int32_t skew = __builtin_amdgcn_readfirstlane(lskew[pg]);
-        const int32_t minc = wave_imin(in_zset ? c : INT32_MAX);
+        const int32_t minc = wave_reduce(in_zset ? c : INT32_MAX, [](int32_t x, int32_t y) { return min(x, y); });
         // cnt + 1 - minc <= max_skew without leaving int32: 0 <= minc <= c on a lane of Zset, 1 <= max_skew
         allowed = __ballot(in_zset && c - minc <= skew - 1);
         av &= hz;
@@ -239,45 +230,22 @@ __global__ __launch_bounds__(NW * WAVE) void seq_spread_kernel(SpreadArgs sa) {
 }
 
 namespace {
-constexpr int SPREAD_NPL2 = 8, SPREAD_NPL4 = 4;  // nodes per thread: up to two resources, three or four
-constexpr int SPREAD_MAX_WAVES = 16;
-
-template <int NR, int NPL, int NW>
-hipError_t launch_spread_nw(const SpreadArgs& a, hipStream_t s) {
-  auto kx = seq_spread_kernel<NR, NPL, NW, true>;
-  auto id = seq_spread_kernel<NR, NPL, NW, false>;
-  const size_t lds = (size_t)a.n_groups * (SPREAD_ZONES + 1) * sizeof(int32_t);  // at most 33,280 bytes
-  if (needs_kx(a.f.s.pp)) MSH_TIMED_LAUNCH(kx, dim3(1), dim3(NW * WAVE), lds, s, a);
-  else MSH_TIMED_LAUNCH(id, dim3(1), dim3(NW * WAVE), lds, s, a);
-  return hipGetLastError();
-}
-
-// as few waves as hold the table: 1, 4 or 16
-template <int NR, int NPL>
-hipError_t launch_spread_nr(const SpreadArgs& a, hipStream_t s) {
-  const int32_t n = a.f.s.n_nodes;
-  if (n <= 1 * WAVE * NPL) return launch_spread_nw<NR, NPL, 1>(a, s);
-  if (n <= 4 * WAVE * NPL) return launch_spread_nw<NR, NPL, 4>(a, s);
-  return launch_spread_nw<NR, NPL, SPREAD_MAX_WAVES>(a, s);
-}
+struct SpreadFamily {
+  static constexpr int NPL2 = 8, NPL4 = 4;  // seq_fit_kernel's
+  template <int NR, int NPL, int NW>
+  static auto kernel(const SpreadArgs& a) {
+    return needs_kx(a.f.s.pp) ? seq_spread_kernel<NR, NPL, NW, true> : seq_spread_kernel<NR, NPL, NW, false>;
+  }
+};
 }  // namespace
 
-int32_t seq_spread_max_nodes(int32_t nres) {
-  return SPREAD_MAX_WAVES * WAVE * (nres <= 2 ? SPREAD_NPL2 : SPREAD_NPL4);
-}
+int32_t seq_spread_max_nodes(int32_t nres) { return seq_frame_max_nodes<SpreadFamily>(nres); }
 
 hipError_t launch_seq_spread(const SpreadArgs& a, hipStream_t s, std::string* err) {
   if (a.f.s.n_pods == 0) return hipSuccess;
   if (a.n_groups < 0 || a.n_groups > SPREAD_MAX_GROUPS) return hipErrorInvalidValue;
-  if (a.f.s.n_nodes > seq_spread_max_nodes(a.f.nres)) {
-    if (err)
-      *err = "the topology-spread form keeps the node state in registers: at most " +
-             std::to_string(seq_spread_max_nodes(a.f.nres)) + " nodes per device with " + std::to_string(a.f.nres) +
-             (a.f.nres == 1 ? " resource" : " resources");
-    return hipErrorInvalidValue;
-  }
-  if (a.f.nres <= 2) return launch_spread_nr<2, SPREAD_NPL2>(a, s);
-  return launch_spread_nr<4, SPREAD_NPL4>(a, s);
+  const size_t lds = (size_t)a.n_groups * (SPREAD_ZONES + 1) * sizeof(int32_t);  // at most 33,280 bytes
+  return launch_seq_frame<SpreadFamily>(a, a.f, "topology-spread", lds, s, err);
 }
 
 }  // namespace msh
