@@ -481,7 +481,8 @@ int msh_seq_fit_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t scored, int3
  * Refusals of a spread call. No zone column: MSH_ERR_STATE (as no node table, and no resource table with nres > 0).
  *   Host form: a group outside [-1, G) (so any group >= 0 with G = 0), a request outside [0, 2^62]:
  *   MSH_ERR_INVALID. MSH_TIEBREAK_RANDOM, a score-column list, a resource score other than NONE:
- *   MSH_ERR_UNSUPPORTED with a message that names the reason (scoring together with spread is not implemented). A
+ *   MSH_ERR_UNSUPPORTED with a message that names the reason (scoring together with spread is not implemented). This
+ *   refusal of a scored ctx stays: msh_schedule_sequential_spread_scored (below) is the call that takes one. A
  *   table past the limit: MSH_ERR_UNSUPPORTED with the limit in the message. The limits are _fit's: 8,192 nodes
  *   for up to two resources, 4,096 for three or four; msh_seq_spread_max_nodes reports them for nres in 0..4.
  * The device form is asynchronous, as msh_schedule_sequential_fit_device, and validates neither d_pod_req nor
@@ -521,6 +522,46 @@ int msh_schedule_sequential_spread_device(msh_ctx* ctx, int32_t p, const int8_t*
                                           const uint8_t* d_pod_tol, const int32_t* d_pod_group, int32_t nres,
                                           const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
                                           int64_t* d_out_score, int32_t* d_out_status, void* stream);
+
+/* Topology spread together with a resource score (upstream's v1.22 default profile on one pod: NodeResourcesFit as
+ * a filter, NodeResourcesLeastAllocated as a score, PodTopologySpread as a filter; additive in ABI 8).
+ * msh_schedule_sequential_spread_scored / _spread_scored_device take msh_schedule_sequential_spread's arguments and
+ * are the superset call: a caller may use them whatever the ctx's resource score mode is.
+ * With mode NONE the call behaves as msh_schedule_sequential_spread / _spread_device in every respect: the same
+ *   kernel instance, limits and refusals, nres = 0 included.
+ * With LEAST_ALLOCATED / MOST_ALLOCATED the two sections above compose. Pods are decided strictly in order; for pod
+ *   j with pg = pod_group[j]:
+ *   The feasible set is _spread's: the filter list, count[i] < eff[i], every positive request fits, and for
+ *   pg >= 0 also zone[i] >= 0 and cnt[pg][zone[i]] + 1 - minc(pg) <= max_skew[pg], minc over Zset.
+ *   The status is _spread's: MSH_FIT_ERROR with no feasible node, otherwise MSH_SCORE_ERROR when NodeNumber scores
+ *   without its PreScore state (commits nothing), otherwise MSH_PLACED.
+ *   A feasible node's total is the scored _fit call's, T(i) + weight * RS(j, i), exactly as written under
+ *   msh_set_resource_score (q = used + req before this pod's commit, truncating int64, a zero capacity or q > c
+ *   scores 0, resources of weight 0 are fitted but not scored). NodeNumber's normalizer extents are taken over the
+ *   feasible list, which is the spread-filtered one.
+ *   The pod goes to the first maximum of total in List order; out_score and commit_cb get that total.
+ *   The commit: count[sel] += 1, used[r][sel] += req[r][j], and for pg >= 0 cnt[pg][zone[sel]] += 1.
+ * Refusals of a scored call, in this order. MSH_TIEBREAK_RANDOM, a score-column list: MSH_ERR_UNSUPPORTED. No node
+ *   table, no zone column, no resource table: MSH_ERR_STATE. nres != the table's: MSH_ERR_INVALID. nres != the
+ *   setting's (so nres = 0 with a score set): MSH_ERR_STATE. A table past the limit: MSH_ERR_UNSUPPORTED with the
+ *   limit in the message; the limits are the scored _fit call's, 4,096 nodes for one or two resources, 2,048 for
+ *   three or four. The ctx's largest written amount above MSH_RESOURCE_SCORE_MAX: MSH_ERR_UNSUPPORTED. Host form: a
+ *   group outside [-1, G), a request outside [0, 2^62] or above MSH_RESOURCE_SCORE_MAX: MSH_ERR_INVALID.
+ * msh_seq_spread_scored_max_nodes reports the limit of the call as the ctx is set now, for nres in 0..4: the scored
+ *   limits with a mode other than NONE, msh_seq_spread_max_nodes' with NONE.
+ * The device form is asynchronous and ordered with the ctx's other sequential launches as _spread_device is; it
+ *   validates neither d_pod_req nor d_pod_group, and the kernel treats every group value outside [0, G) as -1.
+ * A failed call changes nothing. */
+int msh_seq_spread_scored_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t* out_max_nodes);
+int msh_schedule_sequential_spread_scored(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                          const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
+                                          int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+                                          int32_t* out_status, msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_spread_scored_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit,
+                                                 const uint8_t* d_pod_tol, const int32_t* d_pod_group, int32_t nres,
+                                                 const int64_t* d_pod_req, int32_t max_pods_per_node,
+                                                 int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
+                                                 void* stream);
 
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and

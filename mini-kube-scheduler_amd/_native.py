@@ -79,6 +79,8 @@ EXPORTED = (
     "msh_upload_node_zones", "msh_clear_node_zones", "msh_node_zones", "msh_set_spread_groups",
     "msh_get_spread_groups", "msh_spread_counts", "msh_patch_spread_counts", "msh_reset_spread_counts",
     "msh_seq_spread_max_nodes", "msh_schedule_sequential_spread", "msh_schedule_sequential_spread_device",
+    "msh_seq_spread_scored_max_nodes", "msh_schedule_sequential_spread_scored",
+    "msh_schedule_sequential_spread_scored_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -207,6 +209,9 @@ _SIGS = {
     "msh_seq_spread_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_schedule_sequential_spread": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
     "msh_schedule_sequential_spread_device": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "msh_seq_spread_scored_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
+    "msh_schedule_sequential_spread_scored": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_spread_scored_device": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

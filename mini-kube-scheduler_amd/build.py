@@ -36,13 +36,14 @@ SOURCES = [
     ("msh_seq_fit.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_score.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_spread.hip", "hipcc", ["-x", "hip"]),
+    ("msh_seq_spread_score.hip", "hipcc", ["-x", "hip"]),
     ("msh_prep.hip", "hipcc", ["-x", "hip"]),
     ("msh_capi.cpp", "hipcc", []),
     ("msh_shard.cpp", "hipcc", []),
     ("msh_pack.cpp", "g++", []),
 ]
 HEADERS = [CSRC / "msh_internal.h", CSRC / "msh_device.h", CSRC / "msh_pool.h", CSRC / "msh_ctx.h", CSRC / "msh_seq_kernel.h",
-           CSRC / "msh_seq_frame.h", INCLUDE / "minisched_hip.h"]
+           CSRC / "msh_seq_frame.h", CSRC / "msh_seq_score_policy.h", INCLUDE / "minisched_hip.h"]
 
 
 def _hipcc() -> str:

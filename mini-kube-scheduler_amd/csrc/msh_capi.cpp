@@ -1857,15 +1857,43 @@ int msh_seq_spread_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_no
   return MSH_OK;
 }
 
+int msh_seq_spread_scored_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = c->rs_mode != MSH_RESOURCE_SCORE_NONE ? msh::seq_spread_score_max_nodes(nres)
+                                                         : msh::seq_spread_max_nodes(nres);
+  return MSH_OK;
+}
+
 namespace {
-// What a spread call needs, checked before any device work (`entry`: the name for messages).
-int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node) {
+// What a _spread_scored call on a ctx with a resource score needs on top of spread_check's node, zone and table
+// checks: the setting's nres, the scored form's table limit, every written amount within MSH_RESOURCE_SCORE_MAX.
+int spread_scored_check(msh_ctx* c, int32_t nres) {
+  if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+  if (nres != c->rs_nres)
+    return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
+                                      " resources, the call has " + std::to_string(nres));
+  if (c->n_nodes > msh::seq_spread_score_max_nodes(nres))
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                msh::seq_table_limit_message("scored topology-spread", msh::seq_spread_score_max_nodes(nres), nres));
+  if (c->res_max > MSH_RESOURCE_SCORE_MAX)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
+                "or patch wrote " + std::to_string(c->res_max));
+  return MSH_OK;
+}
+
+// What a spread call needs, checked before any device work (`entry`: the name for messages). scored_entry: the
+// call is a _spread_scored one, which takes a ctx with a resource score (spread_scored_check then follows the
+// table checks); the _spread entry points refuse such a ctx.
+int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node,
+                 bool scored_entry) {
   if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
   int rc = refuse_random(c, entry);
   if (rc != MSH_OK) return rc;
   if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
-  if (c->rs_mode != MSH_RESOURCE_SCORE_NONE)
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+  if (scored && !scored_entry)
     return fail(c, MSH_ERR_UNSUPPORTED,
                 std::string(entry) + ": a resource score (msh_set_resource_score) together with topology spread is "
                                      "not implemented (MSH_RESOURCE_SCORE_NONE restores the unscored form)");
@@ -1877,6 +1905,7 @@ int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t
       return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
                                           std::to_string(c->nres));
   }
+  if (scored) return spread_scored_check(c, nres);
   if (c->n_nodes > msh::seq_spread_max_nodes(nres))
     return fail(c, MSH_ERR_UNSUPPORTED,
                 msh::seq_table_limit_message("topology-spread", msh::seq_spread_max_nodes(nres), nres));
@@ -1885,13 +1914,13 @@ int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t
 
 int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
                   const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req, int32_t max_pods_per_node,
-                  int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status, void* stream) {
+                  int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status, void* stream, bool scored_entry) {
   if (!c) return MSH_ERR_INVALID;
   c->err.clear();
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_pod_group || !d_out_idx || !d_out_status))  // d_out_score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
   if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = spread_check(c, entry, p, nres, max_pods_per_node);
+  int rc = spread_check(c, entry, p, nres, max_pods_per_node, scored_entry);
   if (rc != MSH_OK) return rc;
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
@@ -1931,13 +1960,25 @@ int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_
     if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
   std::string err;
   hipError_t e;
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;  // a _spread_scored call: spread_check let it pass
   {
     TimedLaunch tl(c);
-    e = msh::launch_seq_spread(sa, s, &err);
+    if (scored) {  // the same argument block with the setting, as seq_device fills FitScoreArgs
+      msh::SpreadScoreArgs ssa{};
+      ssa.s = sa;
+      ssa.most = c->rs_mode == MSH_RESOURCE_SCORE_MOST_ALLOCATED ? 1 : 0;
+      ssa.weight = c->rs_weight;
+      uint32_t sum = 0;
+      for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(ssa.rw[r] = r < nres ? c->rs_w[r] : 0);
+      ssa.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
+      e = msh::launch_seq_spread_score(ssa, s, &err);
+    } else {
+      e = msh::launch_seq_spread(sa, s, &err);
+    }
   }
   if (e != hipSuccess) {
     if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
-    return hip_fail(c, e, "seq_spread_kernel");
+    return hip_fail(c, e, scored ? "seq_spread_score_kernel" : "seq_spread_kernel");
   }
   c->counts_dirty = false;  // the one workgroup folded the replicas
   return track_launch(c, s, true);
@@ -1949,28 +1990,43 @@ int msh_schedule_sequential_spread_device(msh_ctx* c, int32_t p, const int8_t* d
                                           int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
                                           int32_t* d_out_status, void* stream) {
   return spread_device(c, "msh_schedule_sequential_spread_device", p, d_pod_digit, d_pod_tol, d_pod_group, nres,
-                       d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+                       d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, false);
 }
 
-int msh_schedule_sequential_spread(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                   const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
-                                   int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
-                                   int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  const char* entry = "msh_schedule_sequential_spread";
+int msh_schedule_sequential_spread_scored_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
+                                                 const uint8_t* d_pod_tol, const int32_t* d_pod_group, int32_t nres,
+                                                 const int64_t* d_pod_req, int32_t max_pods_per_node,
+                                                 int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
+                                                 void* stream) {
+  return spread_device(c, "msh_schedule_sequential_spread_scored_device", p, d_pod_digit, d_pod_tol, d_pod_group,
+                       nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, true);
+}
+
+namespace {
+// msh_schedule_sequential_spread and msh_schedule_sequential_spread_scored
+int spread_host(msh_ctx* c, const char* entry, bool scored_entry, int32_t p, const int8_t* pod_digit,
+                const uint8_t* pod_tol, const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
+                int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score, int32_t* out_status,
+                msh_commit_cb commit_cb, void* user) {
   if (!c) return MSH_ERR_INVALID;
   c->err.clear();
   if (p > 0 && (!pod_digit || !pod_tol || !pod_group || !out_idx || !out_status))  // out_score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
   if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
-  int rc = spread_check(c, entry, p, nres, max_pods_per_node);
+  int rc = spread_check(c, entry, p, nres, max_pods_per_node, scored_entry);
   if (rc != MSH_OK) return rc;
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   for (int32_t j = 0; j < p; ++j)
     if (pod_group[j] < -1 || pod_group[j] >= c->sp_groups)
       return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": group " + std::to_string(pod_group[j]) +
                                           " outside [-1, G) with G = " + std::to_string(c->sp_groups));
-  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e)
+  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
     if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
       return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
+    if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
+      return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
+                                          std::to_string(e % (size_t)p));
+  }
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
   HostIO io;
@@ -1983,13 +2039,30 @@ int msh_schedule_sequential_spread(msh_ctx* c, int32_t p, const int8_t* pod_digi
   std::memcpy(c->h_nstage + rbytes, pod_group, (size_t)p * sizeof(int32_t));
   rc = spread_device(c, entry, p, io.d_pd, io.d_pt, reinterpret_cast<const int32_t*>(c->h_nstage + rbytes), nres,
                      reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
-                     io.o_status, c->stream);
+                     io.o_status, c->stream, scored_entry);
   if (rc != MSH_OK) return rc;
   if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
   if (commit_cb)
     for (int32_t j = 0; j < p; j++)
       if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
   return MSH_OK;
+}
+}  // namespace
+
+int msh_schedule_sequential_spread(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                   const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
+                                   int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+                                   int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  return spread_host(c, "msh_schedule_sequential_spread", false, p, pod_digit, pod_tol, pod_group, nres, pod_req,
+                     max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+}
+
+int msh_schedule_sequential_spread_scored(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                          const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
+                                          int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+                                          int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  return spread_host(c, "msh_schedule_sequential_spread_scored", true, p, pod_digit, pod_tol, pod_group, nres,
+                     pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
 }
 
 int msh_keys_slot1_is_any(const msh_ctx* c, int32_t* out_flag) {

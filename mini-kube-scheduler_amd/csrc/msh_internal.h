@@ -288,7 +288,7 @@ struct FitArgs {
   const int64_t* pod_req;  // [nres][s.n_pods]
 };
 // What a call past a register-resident form's table limit is refused with (the launchers and the host checks):
-// form is "resource-fit", "scored resource-fit" or "topology-spread", limit its seq_*_max_nodes(nres).
+// form is "resource-fit", "scored resource-fit", "topology-spread" or "scored topology-spread", limit its seq_*_max_nodes(nres).
 inline std::string seq_table_limit_message(const char* form, int32_t limit, int32_t nres) {
   return std::string("the ") + form + " form keeps the node state in registers: at most " + std::to_string(limit) +
          " nodes per device with " + std::to_string(nres) + (nres == 1 ? " resource" : " resources");
@@ -324,6 +324,19 @@ struct SpreadArgs {
 // Nodes the topology-spread kernel holds for a table of nres resources (0..FIT_MAX_RES): the resource-fit limits.
 int32_t seq_spread_max_nodes(int32_t nres);
 hipError_t launch_seq_spread(const SpreadArgs& a, hipStream_t s, std::string* err);
+// The scored topology-spread form (msh_seq_spread_score.hip, msh_schedule_sequential_spread_scored on a ctx whose
+// resource score mode is not NONE): the topology-spread feasible set with the scored resource-fit form's totals.
+// s.f.nres is 1..FIT_MAX_RES; every amount must be <= 2^55 (checked on the host).
+struct SpreadScoreArgs {
+  SpreadArgs s;
+  int32_t most;             // as FitScoreArgs
+  int64_t weight;
+  int32_t rw[FIT_MAX_RES];
+  uint32_t wsum_magic;
+};
+// Nodes the scored topology-spread kernel holds for a table of nres resources: the scored resource-fit limits.
+int32_t seq_spread_score_max_nodes(int32_t nres);
+hipError_t launch_seq_spread_score(const SpreadScoreArgs& a, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

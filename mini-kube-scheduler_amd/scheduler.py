@@ -491,10 +491,14 @@ class DeviceContext:
         group g is placed only on a node with a zone where cnt[g][zone] + 1 - min over the table's zones of cnt[g]
         stays within max_skew[g]; a placement adds 1 to cnt[g][zone]. pod_req (nres, p) as in
         schedule_sequential_fit, or None: no requests are checked or committed."""
+        return self._spread_host(self._lib.msh_schedule_sequential_spread, "schedule_sequential_spread", pod_digit,
+                                 pod_tol, pod_group, pod_req, max_pods_per_node, on_commit, out)
+
+    def _spread_host(self, fn, name: str, pod_digit, pod_tol, pod_group, pod_req, max_pods_per_node, on_commit, out):
         pod_digit = np.ascontiguousarray(pod_digit, np.int8)
         pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
         pod_group = self._int32s(pod_group, "pod_group")
-        p = _same_len("schedule_sequential_spread", pod_digit, pod_tol, pod_group)
+        p = _same_len(name, pod_digit, pod_tol, pod_group)
         nres = 0
         if pod_req is not None:
             pod_req = self._amounts(pod_req)
@@ -503,7 +507,7 @@ class DeviceContext:
             nres = pod_req.shape[0]
         idx, score, status = self._outputs(p, out)
         cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
-        self._check(self._lib.msh_schedule_sequential_spread(
+        self._check(fn(
             self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), nres,
             N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
         return idx, score, status
@@ -514,6 +518,34 @@ class DeviceContext:
         """msh_schedule_sequential_spread_device (asynchronous on `stream`; d_pod_req and d_pod_group are not
         validated: a group outside [0, G) is an ungrouped pod)."""
         self._check(self._lib.msh_schedule_sequential_spread_device(
+            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group, int(nres), d_pod_req or None,
+            int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+
+    # -- topology spread together with a resource score (the superset call of the sequential entry points) --
+    def seq_spread_scored_max_nodes(self, nres: int = 0) -> int:
+        """msh_seq_spread_scored_max_nodes: the largest table schedule_sequential_spread_scored takes with nres
+        (0..4) resources as the ctx is set now: the scored limits with a resource score, seq_spread_max_nodes'
+        without."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_spread_scored_max_nodes(self.handle, int(nres), C.byref(out)))
+        return out.value
+
+    def schedule_sequential_spread_scored(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_group, pod_req=None,
+                                          max_pods_per_node: int = 0,
+                                          on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_spread_scored: schedule_sequential_spread on a ctx that may hold a resource
+        score. With set_resource_score("least" / "most") the feasible set is schedule_sequential_spread's and a
+        feasible node's total is the scored schedule_sequential_fit's (NodeNumber plus weight x the Least /
+        MostAllocated score); pod_req is then required. With "none" it is schedule_sequential_spread."""
+        return self._spread_host(self._lib.msh_schedule_sequential_spread_scored, "schedule_sequential_spread_scored",
+                                 pod_digit, pod_tol, pod_group, pod_req, max_pods_per_node, on_commit, out)
+
+    def schedule_sequential_spread_scored_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
+                                                 nres: int, d_pod_req: int, max_pods_per_node: int, d_idx: int,
+                                                 d_score: int, d_status: int, stream: int = 0) -> None:
+        """msh_schedule_sequential_spread_scored_device (asynchronous on `stream`; d_pod_req and d_pod_group are
+        not validated: a group outside [0, G) is an ungrouped pod)."""
+        self._check(self._lib.msh_schedule_sequential_spread_scored_device(
             self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group, int(nres), d_pod_req or None,
             int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
 
@@ -722,7 +754,9 @@ class Scheduler:
     `spread_groups` maps a group name to its max_skew, and a pod belongs to the group named by its `spread_label`
     label (default "app"), or to none. A grouped pod is placed only where its group's count in the node's zone stays
     within max_skew of the group's emptiest zone (DeviceContext.schedule_sequential_spread); with `resources` the
-    requests are fitted too. Not available together with resource_score. schedule_batch ignores them.
+    requests are fitted too, and with resource_score the feasible nodes are scored as above
+    (DeviceContext.schedule_sequential_spread_scored, the call schedule_sequential makes whenever groups are
+    configured). schedule_batch ignores them.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
@@ -736,8 +770,6 @@ class Scheduler:
         if (zones is None) != (spread_groups is None):
             raise ValueError("zones and spread_groups go together")
         if spread_groups is not None:
-            if resource_score is not None:
-                raise ValueError("resource_score together with spread_groups is not implemented")
             if len(spread_groups) > N.MAX_SPREAD_GROUPS:
                 raise ValueError(f"spread_groups: at most {N.MAX_SPREAD_GROUPS} groups")
             if any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= N.INT32_MAX for v in spread_groups.values()):
@@ -898,6 +930,6 @@ class Scheduler:
                 self._res_synced = True
             req = np.array([pod_requests(p, self.resources) for p in pods], np.int64)
             req = req.reshape(len(pods), len(self.resources)).T
-        idx, score, status = self.ctx.schedule_sequential_spread(table.digit, table.tolerates, self.pod_group_ids(pods),
-                                                                 req, max_pods_per_node)
+        idx, score, status = self.ctx.schedule_sequential_spread_scored(table.digit, table.tolerates,
+                                                                        self.pod_group_ids(pods), req, max_pods_per_node)
         return self._results(table, idx, score, status)
