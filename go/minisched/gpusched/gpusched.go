@@ -747,6 +747,121 @@ func (x *Ctx) SeqFitMaxNodes(nres int, scored bool) (int, error) {
 	return int(out), nil
 }
 
+// ---- static node filters for sequential mode: per-class node masks ----
+//
+// nodeSelector, required NodeAffinity, TaintToleration (NoSchedule / NoExecute) and NodeName depend only on the
+// pod's spec and the node's name, labels and taints. The caller groups the pods into at most MaxPodClasses classes of
+// identical constraints, evaluates each class against each node once (upstream's own helpers do that in Go:
+// nodeaffinity.GetRequiredNodeAffinity(pod).Match(node), v1helper.FindMatchingUntoleratedTaint) and uploads one
+// uint64 per node in List order: bit c is set if the node admits pods of class c. ScheduleSequentialClasses is
+// msh_schedule_sequential_spread_scored's contract with a class per pod (-1: none); group and class may be nil
+// (no pod has a group / a class; nil groups need no zone column). UploadNodes drops the column; UpdateNodes keeps
+// it; every other call ignores it. Like the rest of this package these calls have not been compiled (go/README.md).
+
+// MaxPodClasses is MSH_MAX_POD_CLASSES.
+const MaxPodClasses = int(C.MSH_MAX_POD_CLASSES)
+
+func toU64(v []uint64) *C.uint64_t {
+	if len(v) == 0 {
+		return nil
+	}
+	return (*C.uint64_t)(unsafe.Pointer(&v[0]))
+}
+
+func toI32(v []int32) []C.int32_t {
+	c := make([]C.int32_t, len(v))
+	for i, x := range v {
+		c[i] = C.int32_t(x)
+	}
+	return c
+}
+
+// UploadNodeClassBits sets the class column for nClasses classes (1..MaxPodClasses; no bit at or above nClasses).
+func (x *Ctx) UploadNodeClassBits(nClasses int, bits []uint64) error {
+	if rc := C.msh_upload_node_class_bits(x.c, C.int32_t(len(bits)), C.int32_t(nClasses), toU64(bits)); rc != C.MSH_OK {
+		return x.lastErr("msh_upload_node_class_bits", rc)
+	}
+	return nil
+}
+
+// PatchNodeClassBits replaces the whole words of the nodes at idx (distinct List-order indices); nothing is rebuilt.
+func (x *Ctx) PatchNodeClassBits(idx []int32, bits []uint64) error {
+	if len(idx) != len(bits) {
+		return errors.New("gpusched: idx / bits length mismatch")
+	}
+	if rc := C.msh_patch_node_class_bits(x.c, C.int32_t(len(idx)), ptrI32(toI32(idx)), toU64(bits)); rc != C.MSH_OK {
+		return x.lastErr("msh_patch_node_class_bits", rc)
+	}
+	return nil
+}
+
+// ClearNodeClassBits goes back to "no column".
+func (x *Ctx) ClearNodeClassBits() error {
+	if rc := C.msh_clear_node_class_bits(x.c); rc != C.MSH_OK {
+		return x.lastErr("msh_clear_node_class_bits", rc)
+	}
+	return nil
+}
+
+// NodeClassBits returns the number of classes and the column (n words, the uploaded node count), or 0 and nil when
+// none is present.
+func (x *Ctx) NodeClassBits(n int) (nClasses int, bits []uint64, err error) {
+	var present, nc C.int32_t
+	out := make([]uint64, n)
+	if rc := C.msh_node_class_bits(x.c, &nc, toU64(out), &present); rc != C.MSH_OK {
+		return 0, nil, x.lastErr("msh_node_class_bits", rc)
+	}
+	if present == 0 {
+		return 0, nil, nil
+	}
+	return int(nc), out, nil
+}
+
+// SeqClassesMaxNodes returns the largest table ScheduleSequentialClasses takes with nres resources as the ctx is
+// set now: the scored limits with a resource score, the topology-spread limits without.
+func (x *Ctx) SeqClassesMaxNodes(nres int) (int, error) {
+	var out C.int32_t
+	if rc := C.msh_seq_classes_max_nodes(x.c, C.int32_t(nres), &out); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_seq_classes_max_nodes", rc)
+	}
+	return int(out), nil
+}
+
+// ScheduleSequentialClasses is ScheduleSequentialFit with a spread group and a class per pod (nil: none has one);
+// req holds nres*len(pods) values (req[r*len(pods)+j]), nres may be 0 without a resource score.
+func (x *Ctx) ScheduleSequentialClasses(pods []*v1.Pod, b *HostBatch, group, class []int32, nres int, req []int64,
+	maxPodsPerNode int32) ([]Result, error) {
+	if !x.hasNodes {
+		return nil, errors.New("gpusched: UploadNodes has not been called")
+	}
+	p := len(pods)
+	if len(req) != nres*p || (group != nil && len(group) != p) || (class != nil && len(class) != p) {
+		return nil, errors.New("gpusched: req holds nres*len(pods) values, group and class len(pods)")
+	}
+	if err := x.pack(b, pods); err != nil {
+		return nil, err
+	}
+	if rc := C.msh_schedule_sequential_classes(x.c, C.int32_t(p), ptrI8(b.pd[:p]), ptrU8(b.pt[:p]), ptrI32(toI32(group)),
+		ptrI32(toI32(class)), C.int32_t(nres), ptrI64(toI64(req)), C.int32_t(maxPodsPerNode), ptrI32(b.idx[:p]),
+		ptrI64(b.score[:p]), ptrI32(b.status[:p]), nil, nil); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_schedule_sequential_classes", rc)
+	}
+	return x.results(b), nil
+}
+
+// ScheduleSequentialClassesDevice is the asynchronous form over device pointers
+// (msh_schedule_sequential_classes_device); dGroup and dClass may be nil, and nothing is validated by the library: a
+// group outside [0, G) is an ungrouped pod, a class outside [0, C) a pod without one.
+func (x *Ctx) ScheduleSequentialClassesDevice(p int, dPodDigit, dPodTol, dGroup, dClass unsafe.Pointer, nres int,
+	dReq unsafe.Pointer, maxPodsPerNode int32, dIdx, dScore, dStatus, stream unsafe.Pointer) error {
+	if rc := C.msh_schedule_sequential_classes_device(x.c, C.int32_t(p), (*C.int8_t)(dPodDigit), (*C.uint8_t)(dPodTol),
+		(*C.int32_t)(dGroup), (*C.int32_t)(dClass), C.int32_t(nres), (*C.int64_t)(dReq), C.int32_t(maxPodsPerNode),
+		(*C.int32_t)(dIdx), (*C.int64_t)(dScore), (*C.int32_t)(dStatus), stream); rc != C.MSH_OK {
+		return x.lastErr("msh_schedule_sequential_classes_device", rc)
+	}
+	return nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

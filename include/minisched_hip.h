@@ -563,6 +563,53 @@ int msh_schedule_sequential_spread_scored_device(msh_ctx* ctx, int32_t p, const 
                                                  int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
                                                  void* stream);
 
+/* Static node filters: per-class node masks (upstream's nodeSelector, required NodeAffinity, TaintToleration for
+ * NoSchedule / NoExecute taints and NodeName; additive in ABI 8). The verdict of each of these filters for a (pod,
+ * node) pair depends only on the pod's spec and the node's labels, taints and name, never on a commit. The host
+ * groups the pods of a call into at most MSH_MAX_POD_CLASSES classes of identical constraints and gives the ctx, per
+ * node, 64 bits: bit c is set if the node admits pods of class c.
+ * The column. bits[i], one uint64 per uploaded node in List order, for C classes, 1 <= C <= MSH_MAX_POD_CLASSES; a
+ *   set bit at or above C is MSH_ERR_INVALID, n different from the uploaded node count MSH_ERR_INVALID, a call before
+ *   msh_upload_nodes MSH_ERR_STATE.
+ * Lifetime and ordering are the capacity column's. msh_upload_nodes drops the column; msh_patch_nodes, the count,
+ *   capacity, resource and zone writers and the count resets keep it. The writers and the reader are synchronous and
+ *   ordered after the ctx's sequential launches in flight; none of them rebuilds the node table.
+ *   msh_patch_node_class_bits replaces the whole words of nodes idx[k] (pairwise distinct, in range; with no column
+ *   MSH_ERR_STATE). msh_clear_node_class_bits returns to "no column". msh_node_class_bits reports *out_present, and
+ *   with a column *out_C and the n words (out_C and out_bits may be NULL).
+ * msh_schedule_sequential_classes / _classes_device are the superset call: msh_schedule_sequential_spread_scored's
+ *   contract and arguments with one more per-pod input, pod_class[j] in [-1, C).
+ *   A pod of class -1 is decided exactly as _spread_scored decides it. For a pod of class c >= 0, node i is feasible
+ *   iff it is feasible for _spread_scored and bit c of bits[i] is set. Everything downstream is taken over this
+ *   feasible set: the status order (MSH_FIT_ERROR, then MSH_SCORE_ERROR, then MSH_PLACED), NodeNumber's normalizer
+ *   extents, the resource score, the first maximum in List order and the commit. A class does not change what a
+ *   commit writes. The spread minimum stays over Zset, as upstream's does.
+ *   pod_class == NULL: every pod has class -1 and no column is needed; with pod_group non-NULL the call is then
+ *   _spread_scored itself, the same kernel instance. pod_class non-NULL without a column: MSH_ERR_STATE.
+ *   pod_group == NULL is allowed here and only here: every pod is ungrouped and no zone column is required. With
+ *   pod_group non-NULL the zone column is required, as in _spread.
+ * Refusals are _spread_scored's, in its order (the class column's MSH_ERR_STATE follows the zone column's). Host
+ *   form: also a class outside [-1, C): MSH_ERR_INVALID. The device form validates nothing: the kernel treats every
+ *   class value outside [0, C) as -1, so no memory is indexed with a pod's raw value.
+ * Node limits are those of the kernel form that runs: msh_seq_classes_max_nodes reports _spread's limits with score
+ *   mode NONE (8,192 nodes up to two resources, 4,096 above) and the scored limits otherwise (4,096 / 2,048).
+ * Every other entry point ignores the column. A failed call changes nothing. */
+#define MSH_MAX_POD_CLASSES 64
+int msh_upload_node_class_bits(msh_ctx* ctx, int32_t n, int32_t C, const uint64_t* bits);
+int msh_patch_node_class_bits(msh_ctx* ctx, int32_t count, const int32_t* idx, const uint64_t* bits);
+int msh_clear_node_class_bits(msh_ctx* ctx);
+int msh_node_class_bits(msh_ctx* ctx, int32_t* out_C, uint64_t* out_bits, int32_t* out_present);
+int msh_seq_classes_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t* out_max_nodes);
+int msh_schedule_sequential_classes(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                    const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                    const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                    int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_classes_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit,
+                                           const uint8_t* d_pod_tol, const int32_t* d_pod_group,
+                                           const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
+                                           int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
+                                           int32_t* d_out_status, void* stream);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

@@ -8,10 +8,12 @@ Import with `importlib.import_module("mini-kube-scheduler_amd")` (the directory 
 a Python identifier).
 """
 from . import _native
+from . import constraints
 from ._native import MshError, device_count
 from .framework import (MAX_NODE_SCORE, NODE_NUMBER, NODE_UNSCHEDULABLE, SCORE_COLUMNS, Code, NodeScore, Normalize,
                         Outcome, ScheduleResult)
 from .scheduler import DeviceContext, DeviceGroup, Scheduler, ScorePluginConfig, pinned_empty
+from .constraints import node_admits
 from .snapshot import NodeTable, PodTable, pack_nodes, pack_pods
 from .queue import (ActionType, ClusterEvent, PodBatch, SchedulingQueue, calculate_backoff_duration,
                     events_to_register)
@@ -23,7 +25,7 @@ from .resultstore import ResultStore
 __all__ = [
     "MAX_NODE_SCORE", "NODE_NUMBER", "NODE_UNSCHEDULABLE", "Code", "NodeScore", "Normalize", "Outcome",
     "ScheduleResult", "DeviceContext", "DeviceGroup", "Scheduler", "ScorePluginConfig", "pinned_empty", "NodeTable", "PodTable",
-    "pack_nodes", "pack_pods", "MshError", "device_count", "_native",
+    "pack_nodes", "pack_pods", "MshError", "device_count", "_native", "constraints", "node_admits",
     "ActionType", "ClusterEvent", "PodBatch", "SchedulingQueue", "calculate_backoff_duration",
     "events_to_register", "NodeCache", "PermitBinder", "CycleReport", "SchedulingLoop",
     "ResultStore",

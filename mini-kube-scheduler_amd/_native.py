@@ -59,6 +59,7 @@ RESOURCE_SCORE_MAX = 1 << 55            # MSH_RESOURCE_SCORE_MAX: the largest am
 
 MAX_ZONES = 64           # MSH_MAX_ZONES: zone ids are in [0, MAX_ZONES), -1 = the node has no zone
 MAX_SPREAD_GROUPS = 128  # MSH_MAX_SPREAD_GROUPS
+MAX_POD_CLASSES = 64     # MSH_MAX_POD_CLASSES: pod classes are in [0, C), C <= MAX_POD_CLASSES, -1 = no class
 
 MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
 MSH_TIEBREAK_RANDOM = 1  # seeded uniform choice among the maxima (msh_set_tiebreak)
@@ -81,6 +82,8 @@ EXPORTED = (
     "msh_seq_spread_max_nodes", "msh_schedule_sequential_spread", "msh_schedule_sequential_spread_device",
     "msh_seq_spread_scored_max_nodes", "msh_schedule_sequential_spread_scored",
     "msh_schedule_sequential_spread_scored_device",
+    "msh_upload_node_class_bits", "msh_patch_node_class_bits", "msh_clear_node_class_bits", "msh_node_class_bits",
+    "msh_seq_classes_max_nodes", "msh_schedule_sequential_classes", "msh_schedule_sequential_classes_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -212,6 +215,13 @@ _SIGS = {
     "msh_seq_spread_scored_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_schedule_sequential_spread_scored": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
     "msh_schedule_sequential_spread_scored_device": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "msh_upload_node_class_bits": (C.c_int, [_P, _I32, _I32, _P]),
+    "msh_patch_node_class_bits": (C.c_int, [_P, _I32, _P, _P]),
+    "msh_clear_node_class_bits": (C.c_int, [_P]),
+    "msh_node_class_bits": (C.c_int, [_P, C.POINTER(_I32), _P, C.POINTER(_I32)]),
+    "msh_seq_classes_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
+    "msh_schedule_sequential_classes": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_classes_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

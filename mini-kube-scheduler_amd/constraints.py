@@ -1,0 +1,187 @@
+"""Static node filters of the v1.22 default profile, evaluated on the host: NodeName, nodeSelector, required node
+affinity and TaintToleration. Their verdict for a (pod, node) pair depends only on the pod's spec and the node's
+name, labels and taints, never on a commit, so the scheduler evaluates them once per (class of pods, node) and
+hands the device one bit per pair (DeviceContext.upload_node_class_bits).
+
+The rules are restated from the published v1.22 sources; each function cites the file and function it follows.
+Objects are k8s-shaped dicts or attribute objects, as in snapshot.py: a node gives metadata.name, metadata.labels
+and spec.taints (or the attributes name, labels, taints), a pod gives spec.nodeName, spec.nodeSelector,
+spec.affinity.nodeAffinity.requiredDuringSchedulingIgnoredDuringExecution.nodeSelectorTerms and spec.tolerations (or
+the attributes node_name, node_selector, node_affinity_terms, tolerations).
+"""
+from __future__ import annotations
+
+import json
+import re
+from typing import Any, Mapping
+
+from .snapshot import _get, _tol_field, node_name, pod_tolerations
+
+_INT64 = re.compile(r"^[+-]?[0-9]+$")  # what strconv.ParseInt(s, 10, 64) takes, before its range check
+_REQUIRED = ("affinity", "nodeAffinity", "requiredDuringSchedulingIgnoredDuringExecution")
+
+
+def node_labels(n: Any) -> Mapping[str, str]:
+    v = n.labels if hasattr(n, "labels") else _get(n, "metadata", "labels")
+    return v or {}
+
+
+def node_taints(n: Any) -> list:
+    v = n.taints if hasattr(n, "taints") else _get(n, "spec", "taints")
+    return list(v or ())
+
+
+def pod_node_name(p: Any) -> str:
+    v = p.node_name if hasattr(p, "node_name") else _get(p, "spec", "nodeName")
+    return v or ""
+
+
+def pod_node_selector(p: Any) -> Mapping[str, str]:
+    v = p.node_selector if hasattr(p, "node_selector") else _get(p, "spec", "nodeSelector")
+    return v or {}
+
+
+def pod_affinity_terms(p: Any) -> list | None:
+    """The required node affinity's nodeSelectorTerms; None when the pod has no required node affinity (an empty
+    list is a required affinity that matches nothing)."""
+    if hasattr(p, "node_affinity_terms"):
+        return None if p.node_affinity_terms is None else list(p.node_affinity_terms)
+    req = _get(p, "spec", *_REQUIRED)
+    if req is None:
+        return None
+    return list(_get(req, "nodeSelectorTerms", default=()) or ())
+
+
+def _parse_int64(s: Any) -> int | None:
+    if not isinstance(s, str) or not _INT64.match(s):
+        return None
+    v = int(s)
+    return v if -(1 << 63) <= v < (1 << 63) else None
+
+
+def fits_node_name(pod: Any, node: Any) -> bool:
+    """pkg/scheduler/framework/plugins/nodename/node_name.go: Fits. spec.nodeName is empty or the node's name."""
+    want = pod_node_name(pod)
+    return want == "" or want == node_name(node)
+
+
+def matches_node_selector(pod: Any, node: Any) -> bool:
+    """component-helpers/scheduling/corev1/nodeaffinity/nodeaffinity.go: GetRequiredNodeAffinity and
+    RequiredNodeAffinity.Match, the labelSelector half (labels.SelectorFromSet of spec.nodeSelector): every
+    key / value pair is present and equal in the node's labels."""
+    labels = node_labels(node)
+    return all(k in labels and str(labels[k]) == str(v) for k, v in pod_node_selector(pod).items())
+
+
+def _expression_matches(e: Any, labels: Mapping[str, str]) -> bool:
+    """component-helpers/scheduling/corev1/nodeaffinity/nodeaffinity.go: nodeSelectorRequirementsAsSelector, then
+    apimachinery/pkg/labels/selector.go: NewRequirement (what makes a requirement invalid) and Requirement.Matches.
+    An invalid requirement makes its term match nothing; here it is simply false, which ANDs to the same."""
+    key, op = _get(e, "key", default=""), _get(e, "operator", default="")
+    values = [str(v) for v in (_get(e, "values", default=()) or ())]
+    has = key in labels
+    if op == "In":
+        return bool(values) and has and str(labels[key]) in values
+    if op == "NotIn":  # matches when the label is absent
+        return bool(values) and not (has and str(labels[key]) in values)
+    if op == "Exists":
+        return not values and has
+    if op == "DoesNotExist":
+        return not values and not has
+    if op in ("Gt", "Lt"):  # exactly one value; both sides base-10 int64, anything else is no match
+        if len(values) != 1 or not has:
+            return False
+        lhs, rhs = _parse_int64(str(labels[key])), _parse_int64(values[0])
+        if lhs is None or rhs is None:
+            return False
+        return lhs > rhs if op == "Gt" else lhs < rhs
+    return False
+
+
+def _field_matches(e: Any, name: str) -> bool:
+    """component-helpers/scheduling/corev1/nodeaffinity/nodeaffinity.go: nodeSelectorRequirementsAsFieldSelector.
+    metadata.name only, In / NotIn only, with exactly one value; anything else is invalid and matches nothing."""
+    values = [str(v) for v in (_get(e, "values", default=()) or ())]
+    if _get(e, "key", default="") != "metadata.name" or len(values) != 1:
+        return False
+    op = _get(e, "operator", default="")
+    if op == "In":
+        return name == values[0]
+    if op == "NotIn":
+        return name != values[0]
+    return False
+
+
+def matches_node_affinity(pod: Any, node: Any) -> bool:
+    """component-helpers/scheduling/corev1/nodeaffinity/nodeaffinity.go: NodeSelector.Match (LazyErrorNodeSelector)
+    over requiredDuringSchedulingIgnoredDuringExecution.nodeSelectorTerms: terms are ORed; within a term
+    matchExpressions and matchFields are ANDed; a term with neither matches nothing (newNodeSelectorTerm /
+    isEmptyNodeSelectorTerm), and so does an empty term list. No required affinity matches every node."""
+    terms = pod_affinity_terms(pod)
+    if terms is None:
+        return True
+    labels, name = node_labels(node), node_name(node)
+    for t in terms:
+        exprs = list(_get(t, "matchExpressions", default=()) or ())
+        fields = list(_get(t, "matchFields", default=()) or ())
+        if not exprs and not fields:
+            continue
+        if all(_expression_matches(e, labels) for e in exprs) and all(_field_matches(f, name) for f in fields):
+            return True
+    return False
+
+
+def toleration_tolerates_taint(tol: Any, taint: Any) -> bool:
+    """k8s.io/api/core/v1/toleration.go: Toleration.ToleratesTaint. An empty effect or the taint's effect; an empty
+    key or the taint's key (validation admits an empty key with operator Exists only); then Exists is true and
+    Equal, or an empty operator, compares the values."""
+    effect, key = _tol_field(tol, "effect"), _tol_field(tol, "key")
+    if effect and effect != _tol_field(taint, "effect"):
+        return False
+    if key and key != _tol_field(taint, "key"):
+        return False
+    op = _tol_field(tol, "operator", "op")
+    if op in ("", "Equal"):
+        return _tol_field(tol, "value") == _tol_field(taint, "value")
+    return op == "Exists"
+
+
+def tolerates_node_taints(pod: Any, node: Any) -> bool:
+    """pkg/scheduler/framework/plugins/tainttoleration/taint_toleration.go: Filter (with
+    component-helpers/scheduling/corev1/helpers.go: FindMatchingUntoleratedTaint): every taint of spec.taints with
+    effect NoSchedule or NoExecute is tolerated by some toleration; PreferNoSchedule never filters.
+    spec.unschedulable is NodeUnschedulable's business, through the pod table's tolerates bit."""
+    tols = pod_tolerations(pod)
+    for taint in node_taints(node):
+        if _tol_field(taint, "effect") not in ("NoSchedule", "NoExecute"):
+            continue
+        if not any(toleration_tolerates_taint(t, taint) for t in tols):
+            return False
+    return True
+
+
+def node_admits(pod: Any, node: Any) -> bool:
+    """The AND of the four static filters: NodeName, nodeSelector, required node affinity, TaintToleration."""
+    return (fits_node_name(pod, node) and matches_node_selector(pod, node) and matches_node_affinity(pod, node)
+            and tolerates_node_taints(pod, node))
+
+
+def _plain(x: Any) -> Any:
+    """A JSON-able copy of the public fields of x (dicts, sequences, attribute objects)."""
+    if isinstance(x, Mapping):
+        return {str(k): _plain(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_plain(v) for v in x]
+    if x is None or isinstance(x, (str, int, float, bool)):
+        return x
+    return {k: _plain(v) for k, v in vars(x).items() if not k.startswith("_")}
+
+
+def class_key(pod: Any) -> str:
+    """The canonical form of what node_admits reads from a pod: (nodeName, nodeSelector, required affinity,
+    tolerations). Pods with equal keys get equal verdicts on every node. Tolerations are reduced to their four
+    fields and sorted (their order does not matter to the filter); affinity terms keep their order."""
+    tols = sorted([_tol_field(t, "key"), _tol_field(t, "operator", "op"), _tol_field(t, "value"),
+                   _tol_field(t, "effect")] for t in pod_tolerations(pod))
+    sel = sorted((str(k), str(v)) for k, v in pod_node_selector(pod).items())
+    return json.dumps([pod_node_name(pod), sel, _plain(pod_affinity_terms(pod)), tols], sort_keys=True)

@@ -414,6 +414,9 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
     c->have_zone = false;  // and the zone column
     c->h_zone.clear();
     c->zset = 0;
+    c->have_class = false;  // and the class masks
+    c->h_class.clear();
+    c->n_classes = 0;
   }
   c->cur = s;
   c->n_nodes = n;
@@ -802,6 +805,7 @@ void msh_destroy(msh_ctx* c) {
   (void)hipFree(c->d_alloc);
   (void)hipFree(c->d_used);
   (void)hipFree(c->d_zone);
+  (void)hipFree(c->d_class);
   (void)hipFree(c->d_skew);
   (void)hipFree(c->d_spread_cnt);
   for (hipEvent_t e : c->async_ev)
@@ -1912,19 +1916,12 @@ int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t
   return MSH_OK;
 }
 
-int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                  const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req, int32_t max_pods_per_node,
-                  int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status, void* stream, bool scored_entry) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_pod_group || !d_out_idx || !d_out_status))  // d_out_score optional
-    return fail(c, MSH_ERR_INVALID, "null device pointer");
-  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = spread_check(c, entry, p, nres, max_pods_per_node, scored_entry);
-  if (rc != MSH_OK) return rc;
-  if (p == 0) return MSH_OK;
-  DeviceGuard g(c->device);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// The argument block of the spread kernels for the ctx as it stands (the class forms take the same block: a null
+// d_pod_group then goes with no groups, and the zone column may be absent).
+msh::SpreadArgs spread_args(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                            const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req,
+                            int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
+                            int32_t* d_out_status) {
   msh::SpreadArgs sa{};
   msh::SeqArgs& a = sa.f.s;
   a.planes = cur_table(c).d_planes;
@@ -1949,12 +1946,39 @@ int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_
   sa.f.alloc = nres ? c->d_alloc : nullptr;
   sa.f.used = nres ? c->d_used : nullptr;
   sa.f.pod_req = nres ? d_pod_req : nullptr;
-  sa.zone = c->d_zone;
+  sa.zone = c->have_zone ? c->d_zone : nullptr;
   sa.pod_group = d_pod_group;
-  sa.n_groups = c->sp_groups;
+  sa.n_groups = d_pod_group ? c->sp_groups : 0;
   sa.max_skew = c->d_skew;
   sa.cnt = c->d_spread_cnt;
-  sa.zset = c->zset;
+  sa.zset = c->have_zone ? c->zset : 0;
+  return sa;
+}
+
+// the ctx's resource score setting (mode LEAST or MOST) for a scored launch with nres resources
+void spread_score_setting(const msh_ctx* c, int32_t nres, msh::SpreadScoreArgs& ssa) {
+  ssa.most = c->rs_mode == MSH_RESOURCE_SCORE_MOST_ALLOCATED ? 1 : 0;
+  ssa.weight = c->rs_weight;
+  uint32_t sum = 0;
+  for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(ssa.rw[r] = r < nres ? c->rs_w[r] : 0);
+  ssa.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
+}
+
+int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                  const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req, int32_t max_pods_per_node,
+                  int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status, void* stream, bool scored_entry) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_pod_group || !d_out_idx || !d_out_status))  // d_out_score optional
+    return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
+  int rc = spread_check(c, entry, p, nres, max_pods_per_node, scored_entry);
+  if (rc != MSH_OK) return rc;
+  if (p == 0) return MSH_OK;
+  DeviceGuard g(c->device);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const msh::SpreadArgs sa = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node,
+                                         d_out_idx, d_out_score, d_out_status);
   // one sequential launch of a ctx at a time (seq_device): each commits into the same counts
   for (auto& ev : c->seq_inflight)
     if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
@@ -1966,11 +1990,7 @@ int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_
     if (scored) {  // the same argument block with the setting, as seq_device fills FitScoreArgs
       msh::SpreadScoreArgs ssa{};
       ssa.s = sa;
-      ssa.most = c->rs_mode == MSH_RESOURCE_SCORE_MOST_ALLOCATED ? 1 : 0;
-      ssa.weight = c->rs_weight;
-      uint32_t sum = 0;
-      for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(ssa.rw[r] = r < nres ? c->rs_w[r] : 0);
-      ssa.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
+      spread_score_setting(c, nres, ssa);
       e = msh::launch_seq_spread_score(ssa, s, &err);
     } else {
       e = msh::launch_seq_spread(sa, s, &err);
@@ -2063,6 +2083,266 @@ int msh_schedule_sequential_spread_scored(msh_ctx* c, int32_t p, const int8_t* p
                                           int32_t* out_status, msh_commit_cb commit_cb, void* user) {
   return spread_host(c, "msh_schedule_sequential_spread_scored", true, p, pod_digit, pod_tol, pod_group, nres,
                      pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+}
+
+// The per-class node masks (msh_schedule_sequential_classes). The column is the capacity column's in lifetime and
+// ordering: unversioned, written through prep_stream behind the sequential launches in flight, which read it at
+// their start, and each writer finishes before it returns.
+namespace {
+// a device column of n_pad words; a larger one is allocated before the old one is let go, so a failure changes nothing
+int class_reserve(msh_ctx* c) {
+  if ((size_t)c->n_pad <= c->class_cap) return MSH_OK;
+  uint64_t* d = nullptr;
+  MSH_HIP(c, hipMalloc(&d, (size_t)c->n_pad * sizeof(uint64_t)));
+  wait_events(c->seq_inflight);
+  (void)hipFree(c->d_class);
+  c->d_class = d;
+  c->class_cap = (size_t)c->n_pad;
+  c->have_class = false;  // the old column went with its buffer
+  c->h_class.clear();
+  c->n_classes = 0;
+  return MSH_OK;
+}
+
+// the whole column from `bits` (n_nodes words; the padding slots 0: they never hold a node)
+int class_write_all(msh_ctx* c, const uint64_t* bits) {
+  const size_t bytes = (size_t)c->n_nodes * sizeof(uint64_t);
+  int rc = node_stage(c, bytes);
+  if (rc != MSH_OK) return rc;
+  if ((rc = after_seq(c)) != MSH_OK) return rc;
+  MSH_HIP(c, hipMemsetAsync(c->d_class, 0, c->class_cap * sizeof(uint64_t), c->prep_stream));
+  if (bytes > 0) {
+    std::memcpy(c->h_nstage, bits, bytes);
+    MSH_HIP(c, hipMemcpyAsync(c->d_class, c->h_nstage, bytes, hipMemcpyHostToDevice, c->prep_stream));
+  }
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+
+bool class_bits_above(uint64_t w, int32_t C) { return C < MSH_MAX_POD_CLASSES && (w >> C) != 0; }
+}  // namespace
+
+int msh_upload_node_class_bits(msh_ctx* c, int32_t n, int32_t C, const uint64_t* bits) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (n != c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "class column of " + std::to_string(n) + " entries for " +
+                                        std::to_string(c->n_nodes) + " uploaded nodes");
+  if (C < 1 || C > MSH_MAX_POD_CLASSES) return fail(c, MSH_ERR_INVALID, "C outside [1, MSH_MAX_POD_CLASSES]");
+  if (n > 0 && !bits) return fail(c, MSH_ERR_INVALID, "null class bits array");
+  for (int32_t i = 0; i < n; ++i)
+    if (class_bits_above(bits[i], C))
+      return fail(c, MSH_ERR_INVALID, "a bit at or above C = " + std::to_string(C) + " is set at node " + std::to_string(i));
+  DeviceGuard g(c->device);
+  int rc = class_reserve(c);
+  if (rc != MSH_OK) return rc;
+  std::vector<uint64_t> h(bits, bits + n);
+  c->have_class = false;  // a failed copy leaves no column
+  if ((rc = class_write_all(c, h.data())) != MSH_OK) return rc;
+  c->h_class.swap(h);
+  c->n_classes = C;
+  c->have_class = true;
+  return MSH_OK;
+}
+
+int msh_patch_node_class_bits(msh_ctx* c, int32_t count, const int32_t* idx, const uint64_t* bits) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (!c->have_class) return fail(c, MSH_ERR_STATE, "msh_upload_node_class_bits has not been called");
+  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
+  if (count == 0) return MSH_OK;
+  if (!idx || !bits) return fail(c, MSH_ERR_INVALID, "null patch arrays");
+  std::vector<int32_t> sorted(idx, idx + count);
+  std::sort(sorted.begin(), sorted.end());
+  if (sorted.front() < 0 || sorted.back() >= c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "patch index outside [0, n)");
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return fail(c, MSH_ERR_INVALID, "duplicate patch index");
+  for (int32_t k = 0; k < count; ++k)
+    if (class_bits_above(bits[k], c->n_classes))
+      return fail(c, MSH_ERR_INVALID, "a bit at or above C = " + std::to_string(c->n_classes) +
+                                          " is set at patch entry " + std::to_string(k));
+  DeviceGuard g(c->device);
+  // the patched column whole: 64 KB at the largest table a class call takes, one copy
+  std::vector<uint64_t> h(c->h_class);
+  for (int32_t k = 0; k < count; ++k) h[(size_t)idx[k]] = bits[k];
+  int rc = class_write_all(c, h.data());
+  if (rc != MSH_OK) {
+    c->have_class = false;  // the device column is in an unknown state
+    return rc;
+  }
+  c->h_class.swap(h);
+  return MSH_OK;
+}
+
+int msh_clear_node_class_bits(msh_ctx* c) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  c->have_class = false;  // launches in flight keep reading the device column, which stays allocated
+  c->h_class.clear();
+  c->n_classes = 0;
+  return MSH_OK;
+}
+
+int msh_node_class_bits(msh_ctx* c, int32_t* out_C, uint64_t* out_bits, int32_t* out_present) {
+  if (!c || !out_present) return MSH_ERR_INVALID;
+  c->err.clear();
+  *out_present = c->have_class ? 1 : 0;
+  if (out_C) *out_C = c->have_class ? c->n_classes : 0;
+  if (c->have_class && out_bits) std::copy(c->h_class.begin(), c->h_class.end(), out_bits);
+  return MSH_OK;
+}
+
+int msh_seq_classes_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = msh::seq_classes_max_nodes(nres, c->rs_mode != MSH_RESOURCE_SCORE_NONE);
+  return MSH_OK;
+}
+
+namespace {
+// What a classes call needs, checked before any device work: _spread_scored's refusals in its order, with the zone
+// column required only when the call has groups, the class column only when it has classes, and the class
+// kernels' table limits.
+int classes_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node, bool grouped,
+                  bool classed) {
+  if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
+  if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
+  int rc = refuse_random(c, entry);
+  if (rc != MSH_OK) return rc;
+  if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (grouped && !c->have_zone) return fail(c, MSH_ERR_STATE, "msh_upload_node_zones has not been called");
+  if (classed && !c->have_class) return fail(c, MSH_ERR_STATE, "msh_upload_node_class_bits has not been called");
+  if (nres) {
+    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+    if (nres != c->nres)
+      return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
+                                          std::to_string(c->nres));
+  }
+  if (scored) {
+    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+    if (nres != c->rs_nres)
+      return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
+                                        " resources, the call has " + std::to_string(nres));
+  }
+  const int32_t lim = msh::seq_classes_max_nodes(nres, scored);
+  if (c->n_nodes > lim)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                msh::seq_table_limit_message(scored ? "scored class-mask" : "class-mask", lim, nres));
+  if (scored && c->res_max > MSH_RESOURCE_SCORE_MAX)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
+                "or patch wrote " + std::to_string(c->res_max));
+  return MSH_OK;
+}
+
+int classes_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                   const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
+                   int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
+                   void* stream) {
+  if (!c) return MSH_ERR_INVALID;
+  // no classes in the call: _spread_scored itself, the same kernel instance
+  if (!d_pod_class && d_pod_group)
+    return spread_device(c, entry, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
+                         d_out_score, d_out_status, stream, true);
+  c->err.clear();
+  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // group, class and score optional
+    return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
+  int rc = classes_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr);
+  if (rc != MSH_OK) return rc;
+  if (p == 0) return MSH_OK;
+  DeviceGuard g(c->device);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+  msh::ClassArgs ca{};
+  ca.ss.s = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
+                        d_out_score, d_out_status);
+  if (scored) spread_score_setting(c, nres, ca.ss);
+  ca.class_bits = d_pod_class ? c->d_class : nullptr;
+  ca.pod_class = d_pod_class;
+  ca.n_classes = d_pod_class ? c->n_classes : 0;
+  // one sequential launch of a ctx at a time (seq_device): each commits into the same counts
+  for (auto& ev : c->seq_inflight)
+    if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
+  std::string err;
+  hipError_t e;
+  {
+    TimedLaunch tl(c);
+    e = msh::launch_seq_classes(ca, scored, s, &err);
+  }
+  if (e != hipSuccess) {
+    if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
+    return hip_fail(c, e, scored ? "seq_classes_score_kernel" : "seq_classes_kernel");
+  }
+  c->counts_dirty = false;  // the one workgroup folded the replicas
+  return track_launch(c, s, true);
+}
+}  // namespace
+
+int msh_schedule_sequential_classes_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                           const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
+                                           const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
+                                           int64_t* d_out_score, int32_t* d_out_status, void* stream) {
+  return classes_device(c, "msh_schedule_sequential_classes_device", p, d_pod_digit, d_pod_tol, d_pod_group,
+                        d_pod_class, nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+}
+
+int msh_schedule_sequential_classes(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                    const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                    const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                    int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  const char* entry = "msh_schedule_sequential_classes";
+  if (!c) return MSH_ERR_INVALID;
+  if (!pod_class && pod_group)  // no classes in the call: _spread_scored itself
+    return spread_host(c, entry, true, p, pod_digit, pod_tol, pod_group, nres, pod_req, max_pods_per_node, out_idx,
+                       out_score, out_status, commit_cb, user);
+  c->err.clear();
+  if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // group, class and score optional
+    return fail(c, MSH_ERR_INVALID, "null host pointer");
+  if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
+  int rc = classes_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr);
+  if (rc != MSH_OK) return rc;
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+  for (int32_t j = 0; pod_group && j < p; ++j)
+    if (pod_group[j] < -1 || pod_group[j] >= c->sp_groups)
+      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": group " + std::to_string(pod_group[j]) +
+                                          " outside [-1, G) with G = " + std::to_string(c->sp_groups));
+  for (int32_t j = 0; pod_class && j < p; ++j)
+    if (pod_class[j] < -1 || pod_class[j] >= c->n_classes)
+      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": class " + std::to_string(pod_class[j]) +
+                                          " outside [-1, C) with C = " + std::to_string(c->n_classes));
+  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
+    if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
+      return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
+    if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
+      return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
+                                          std::to_string(e % (size_t)p));
+  }
+  if (p == 0) return MSH_OK;
+  DeviceGuard g(c->device);
+  HostIO io;
+  if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
+  // the requests, groups and classes through the page-locked node stage, which the kernel reads itself (spread_host)
+  const size_t rbytes = (size_t)nres * (size_t)p * sizeof(int64_t), cbytes = (size_t)p * sizeof(int32_t);
+  if ((rc = node_stage(c, rbytes + 2 * cbytes)) != MSH_OK) return rc;
+  if (rbytes) std::memcpy(c->h_nstage, pod_req, rbytes);
+  int32_t* sg = reinterpret_cast<int32_t*>(c->h_nstage + rbytes);
+  int32_t* sc = reinterpret_cast<int32_t*>(c->h_nstage + rbytes + cbytes);
+  if (pod_group) std::memcpy(sg, pod_group, cbytes);
+  if (pod_class) std::memcpy(sc, pod_class, cbytes);
+  rc = classes_device(c, entry, p, io.d_pd, io.d_pt, pod_group ? sg : nullptr, pod_class ? sc : nullptr, nres,
+                      reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
+                      io.o_status, c->stream);
+  if (rc != MSH_OK) return rc;
+  if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
+  if (commit_cb)
+    for (int32_t j = 0; j < p; j++)
+      if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
+  return MSH_OK;
 }
 
 int msh_keys_slot1_is_any(const msh_ctx* c, int32_t* out_flag) {

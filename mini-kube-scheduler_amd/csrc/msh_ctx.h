@@ -115,6 +115,15 @@ struct msh_ctx {
   std::vector<int32_t> h_skew;
   int32_t* d_skew = nullptr;
   int32_t* d_spread_cnt = nullptr;
+  // the per-class node masks (msh_upload_node_class_bits), unversioned like the capacity column: class_cap uint64
+  // on the device (the padding slots 0), the host copy (n_nodes words, what msh_node_class_bits returns) and the
+  // number of classes C the column was uploaded for; dropped by msh_upload_nodes. Only
+  // msh_schedule_sequential_classes reads it.
+  uint64_t* d_class = nullptr;
+  size_t class_cap = 0;
+  bool have_class = false;
+  int32_t n_classes = 0;
+  std::vector<uint64_t> h_class;
   // per caller stream, the event of its last sequential launch: an alias of a table version's reader
   // event (not owned here; track_launch)
   std::vector<std::pair<hipStream_t, hipEvent_t>> seq_inflight;

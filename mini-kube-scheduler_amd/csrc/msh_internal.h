@@ -288,7 +288,8 @@ struct FitArgs {
   const int64_t* pod_req;  // [nres][s.n_pods]
 };
 // What a call past a register-resident form's table limit is refused with (the launchers and the host checks):
-// form is "resource-fit", "scored resource-fit", "topology-spread" or "scored topology-spread", limit its seq_*_max_nodes(nres).
+// form is "resource-fit", "scored resource-fit", "topology-spread", "scored topology-spread", "class-mask" or
+// "scored class-mask", limit its seq_*_max_nodes(nres).
 inline std::string seq_table_limit_message(const char* form, int32_t limit, int32_t nres) {
   return std::string("the ") + form + " form keeps the node state in registers: at most " + std::to_string(limit) +
          " nodes per device with " + std::to_string(nres) + (nres == 1 ? " resource" : " resources");
@@ -337,6 +338,20 @@ struct SpreadScoreArgs {
 // Nodes the scored topology-spread kernel holds for a table of nres resources: the scored resource-fit limits.
 int32_t seq_spread_score_max_nodes(int32_t nres);
 hipError_t launch_seq_spread_score(const SpreadScoreArgs& a, hipStream_t s, std::string* err);
+// The class forms (msh_seq_classes.hip, msh_schedule_sequential_classes): the topology-spread form (scored: the
+// scored topology-spread form, ss's setting; else ss.most, weight, rw and wsum_magic are not read) with the
+// per-class node mask as one more conjunct. ss.s.zone may be null (no node has a zone) and ss.s.pod_group may be
+// null (every pod ungrouped; n_groups is then 0).
+constexpr int CLASS_MAX = 64;  // MSH_MAX_POD_CLASSES
+struct ClassArgs {
+  SpreadScoreArgs ss;
+  const uint64_t* class_bits;  // [ss.s.f.s.n_words * 32]: bit c: the node admits pods of class c (padding 0), or null
+  const int32_t* pod_class;    // [ss.s.f.s.n_pods]: any value outside [0, n_classes) is a pod without a class, or null
+  int32_t n_classes;           // 0..CLASS_MAX
+};
+// Nodes the class kernels hold: the topology-spread limits unscored, the scored topology-spread limits scored.
+int32_t seq_classes_max_nodes(int32_t nres, bool scored);
+hipError_t launch_seq_classes(const ClassArgs& a, bool scored, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

@@ -22,8 +22,9 @@ from typing import Any, Callable, Iterable, Mapping, Sequence
 import numpy as np
 
 from . import _native as N
+from . import constraints as K
 from .framework import (NODE_NUMBER, NODE_UNSCHEDULABLE, SCORE_COLUMNS, Normalize, Outcome, ScheduleResult)
-from .snapshot import NodeTable, PodTable, _get, node_allocatable, pack_nodes, pack_pods, pod_requests
+from .snapshot import NodeTable, PodTable, _get, _tol_field, node_allocatable, pack_nodes, pack_pods, pod_requests
 
 FILTER_IDS = {NODE_UNSCHEDULABLE: N.MSH_PLUGIN_NODE_UNSCHEDULABLE}
 SCORE_IDS = {NODE_NUMBER: N.MSH_PLUGIN_NODE_NUMBER,
@@ -549,6 +550,92 @@ class DeviceContext:
             self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group, int(nres), d_pod_req or None,
             int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
 
+    # -- static node filters: per-class node masks (nodeSelector, required affinity, taints, nodeName) --
+    @staticmethod
+    def _class_bits(bits) -> np.ndarray:
+        a = np.asarray(bits)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("class bits: a one-dimensional integer array")
+        if a.size and a.dtype != np.uint64 and (int(a.min()) < 0 or int(a.max()) >= 1 << 64):
+            raise ValueError("class bits: integers within uint64")
+        return np.ascontiguousarray(a, np.uint64)
+
+    def upload_node_class_bits(self, n_classes: int, bits) -> None:
+        """msh_upload_node_class_bits: one uint64 per uploaded node, List order; bit c < n_classes is set if the node
+        admits pods of class c (1 <= n_classes <= MAX_POD_CLASSES, no bit at or above n_classes). upload_nodes drops
+        the column; patch_nodes, the count, capacity, resource and zone writers keep it; only
+        schedule_sequential_classes reads it."""
+        bits = self._class_bits(bits)
+        self._check(self._lib.msh_upload_node_class_bits(self.handle, len(bits), int(n_classes), N.ptr(bits)))
+
+    def patch_node_class_bits(self, idx, bits) -> None:
+        """msh_patch_node_class_bits: bits[k] replaces node idx[k]'s whole word (distinct indices within the table;
+        a column must be present). No table rebuild."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        bits = self._class_bits(bits)
+        if len(idx) != len(bits):
+            raise ValueError("idx / bits length mismatch")
+        self._check(self._lib.msh_patch_node_class_bits(self.handle, len(idx), N.ptr(idx), N.ptr(bits)))
+
+    def clear_node_class_bits(self) -> None:
+        """msh_clear_node_class_bits: back to "no column"."""
+        self._check(self._lib.msh_clear_node_class_bits(self.handle))
+
+    def node_class_bits(self) -> tuple[int, np.ndarray] | None:
+        """msh_node_class_bits: (n_classes, the column as uint64 in List order), or None when no column is present."""
+        present, nc = C.c_int32(0), C.c_int32(0)
+        out = np.zeros(self.n_nodes, np.uint64)
+        self._check(self._lib.msh_node_class_bits(self.handle, C.byref(nc), N.ptr(out) if self.n_nodes else None,
+                                                  C.byref(present)))
+        return (nc.value, out) if present.value else None
+
+    def seq_classes_max_nodes(self, nres: int = 0) -> int:
+        """msh_seq_classes_max_nodes: the largest table schedule_sequential_classes takes with nres (0..4) resources
+        as the ctx is set now: the scored limits with a resource score, seq_spread_max_nodes' without."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_classes_max_nodes(self.handle, int(nres), C.byref(out)))
+        return out.value
+
+    def schedule_sequential_classes(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_group=None, pod_class=None,
+                                    pod_req=None, max_pods_per_node: int = 0,
+                                    on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_classes: schedule_sequential_spread_scored with a class per pod (-1: none). A pod of
+        class c >= 0 is placed only on a node whose bit c is set in the class column; everything else (status, the
+        normalizer's extents, the score, the tie-break, the commit) is taken over that feasible set. pod_class None:
+        no pod has a class and no column is needed. pod_group None: no pod has a group and no zone column is
+        needed."""
+        pod_digit = np.ascontiguousarray(pod_digit, np.int8)
+        pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
+        cols = [pod_digit, pod_tol]
+        if pod_group is not None:
+            pod_group = self._int32s(pod_group, "pod_group")
+            cols.append(pod_group)
+        if pod_class is not None:
+            pod_class = self._int32s(pod_class, "pod_class")
+            cols.append(pod_class)
+        p = _same_len("schedule_sequential_classes", *cols)
+        nres = 0
+        if pod_req is not None:
+            pod_req = self._amounts(pod_req)
+            if pod_req.shape[1] != p:
+                raise ValueError("pod_req is shaped (nres, p)")
+            nres = pod_req.shape[0]
+        idx, score, status = self._outputs(p, out)
+        cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
+        self._check(self._lib.msh_schedule_sequential_classes(
+            self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), N.ptr(pod_class), nres,
+            N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
+        return idx, score, status
+
+    def schedule_sequential_classes_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
+                                           d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
+                                           d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
+        """msh_schedule_sequential_classes_device (asynchronous on `stream`; d_pod_group and d_pod_class may be 0;
+        nothing is validated: a group outside [0, G) is an ungrouped pod, a class outside [0, C) a pod without one)."""
+        self._check(self._lib.msh_schedule_sequential_classes_device(
+            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
+            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):
     # ctypes argument conversion cost ~0.9 us per call next to a ~2.6 us launch.
@@ -757,6 +844,13 @@ class Scheduler:
     requests are fitted too, and with resource_score the feasible nodes are scored as above
     (DeviceContext.schedule_sequential_spread_scored, the call schedule_sequential makes whenever groups are
     configured). schedule_batch ignores them.
+
+    The static node filters of the default profile need no configuration: schedule_sequential reads spec.nodeName,
+    spec.nodeSelector, the required node affinity and spec.tolerations of every pod and the name, labels and
+    spec.taints of every node (constraints.node_admits), groups the pods into at most 64 classes of equal
+    constraints per node snapshot and, whenever some pod of the call has a class that some node does not admit,
+    makes the class call (DeviceContext.schedule_sequential_classes) with whatever else is configured. A call
+    whose pods are admitted everywhere is made exactly as before. schedule_batch ignores them.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
@@ -799,7 +893,13 @@ class Scheduler:
         self.nodes: NodeTable | None = None
         self._cap_synced = False  # the snapshot's capacity column is on the device
         self._res_synced = False  # the snapshot's allocatable amounts are on the device
-        self._node_objs: list[Any] = []  # the snapshot's nodes in List order (resources only)
+        self._node_objs: list[Any] = []  # the snapshot's nodes in List order
+        # static node filters (constraints.node_admits): the classes of the pods seen against this snapshot, by
+        # constraints.class_key: an id in [0, MAX_POD_CLASSES), or -1 for a class that every node admits
+        self._class_ids: dict[str, int] = {}
+        self._class_masks: list[np.ndarray] = []  # per id, the nodes (List order) that admit the class
+        self._class_synced = False  # the masks are on the device
+        self._tainted: bool | None = None  # a node of the snapshot has a NoSchedule / NoExecute taint (None: not looked yet)
 
     @staticmethod
     def _resource_weights(resources, resource_score, resource_weights) -> list[int] | None:
@@ -833,15 +933,14 @@ class Scheduler:
 
     # Replaces the per-cycle Nodes().List (minisched.go:40) with one device upload.
     def update_nodes(self, nodes: Iterable[Any]) -> NodeTable:
-        if self.resources is not None or self.zones is not None:
-            nodes = list(nodes)
+        nodes = list(nodes)
         self.nodes = pack_nodes(nodes)
-        self.ctx.upload_nodes(self.nodes.unsched, self.nodes.digit)  # drops the device's capacity column and resources
+        self.ctx.upload_nodes(self.nodes.unsched, self.nodes.digit)  # drops the device's columns and resources
         self._cap_synced = False
         self._res_synced = False
         self._zone_synced = False
-        if self.resources is not None or self.zones is not None:
-            self._node_objs = [nodes[i] for i in self.nodes.order]
+        self._node_objs = [nodes[i] for i in self.nodes.order]
+        self._class_ids, self._class_masks, self._class_synced, self._tainted = {}, [], False, None
         return self.nodes
 
     def _results(self, pods: PodTable, idx, score, status) -> list[ScheduleResult]:
@@ -880,12 +979,14 @@ class Scheduler:
             self.update_nodes(nodes)
         if self.nodes is None:
             raise N.MshError(N.MSH_ERR_STATE, "no node snapshot: call update_nodes() first")
-        if self.resources is not None or self.zones is not None:
-            pods = list(pods)
+        pods = list(pods)
         table = pack_pods(pods)
         if self.nodes.allocatable_pods is not None and not self._cap_synced:
             self.ctx.upload_node_capacity(self.nodes.allocatable_pods)
             self._cap_synced = True
+        classes = self.pod_class_ids(pods)
+        if (classes >= 0).any():  # a pod that some node does not admit: the class call, whatever else is configured
+            return self._schedule_classes(pods, table, classes, max_pods_per_node)
         if self.resources is None and self.zones is None:
             idx, score, status = self.ctx.schedule_sequential(table.digit, table.tolerates, max_pods_per_node)
             return self._results(table, idx, score, status)
@@ -918,8 +1019,46 @@ class Scheduler:
         labels = [_get(p, "metadata", "labels", self.spread_label) for p in pods]
         return np.array([-1 if v is None else self._group_ids.get(str(v), -1) for v in labels], np.int32).reshape(len(pods))
 
-    def _schedule_spread(self, pods, table, max_pods_per_node: int) -> list[ScheduleResult]:
-        if not self._zone_synced:
+    def pod_class_ids(self, pods: Sequence[Any]) -> np.ndarray:
+        """A pod's class for the static node filters (constraints.node_admits: NodeName, nodeSelector, required node
+        affinity, TaintToleration): pods with equal constraints.class_key share an id, ids persist for the node
+        snapshot, and a class that every node admits is -1. More than MAX_POD_CLASSES classes that some node does
+        not admit raise ValueError."""
+        if self._tainted is None:
+            self._tainted = any(_tol_field(t, "effect") in ("NoSchedule", "NoExecute")
+                                for n in self._node_objs for t in K.node_taints(n))
+        out = np.full(len(pods), -1, np.int32)
+        for j, p in enumerate(pods):
+            # without taints the tolerations decide nothing: a pod with no other constraint needs no key
+            if not self._tainted and not (K.pod_node_name(p) or K.pod_node_selector(p)
+                                          or K.pod_affinity_terms(p) is not None):
+                continue
+            key = K.class_key(p)
+            cid = self._class_ids.get(key)
+            if cid is None:
+                mask = np.array([K.node_admits(p, n) for n in self._node_objs], bool).reshape(len(self._node_objs))
+                cid = -1
+                if not mask.all():
+                    if len(self._class_masks) >= N.MAX_POD_CLASSES:
+                        raise ValueError(f"more than {N.MAX_POD_CLASSES} classes of node constraints "
+                                         f"(MAX_POD_CLASSES) against one node snapshot")
+                    cid = len(self._class_masks)
+                    self._class_masks.append(mask)
+                    self._class_synced = False
+                self._class_ids[key] = cid
+            out[j] = cid
+        return out
+
+    def node_class_bits(self) -> np.ndarray:
+        """The snapshot's class column (List order): bit c of word i is set if node i admits class c."""
+        bits = np.zeros(len(self._node_objs), np.uint64)
+        for c, mask in enumerate(self._class_masks):
+            bits |= mask.astype(np.uint64) << np.uint64(c)
+        return bits
+
+    def _sync_spread_inputs(self, pods):
+        """The zone column and the resource table on the device; the call's requests, or None without resources."""
+        if self.zones is not None and not self._zone_synced:
             self.ctx.upload_node_zones(self.node_zone_ids()[0])
             self._zone_synced = True
         req = None
@@ -930,6 +1069,20 @@ class Scheduler:
                 self._res_synced = True
             req = np.array([pod_requests(p, self.resources) for p in pods], np.int64)
             req = req.reshape(len(pods), len(self.resources)).T
+        return req
+
+    def _schedule_classes(self, pods, table, classes, max_pods_per_node: int) -> list[ScheduleResult]:
+        req = self._sync_spread_inputs(pods)
+        if not self._class_synced:
+            self.ctx.upload_node_class_bits(len(self._class_masks), self.node_class_bits())
+            self._class_synced = True
+        groups = self.pod_group_ids(pods) if self.zones is not None else None
+        idx, score, status = self.ctx.schedule_sequential_classes(table.digit, table.tolerates, groups, classes, req,
+                                                                  max_pods_per_node)
+        return self._results(table, idx, score, status)
+
+    def _schedule_spread(self, pods, table, max_pods_per_node: int) -> list[ScheduleResult]:
+        req = self._sync_spread_inputs(pods)
         idx, score, status = self.ctx.schedule_sequential_spread_scored(table.digit, table.tolerates,
                                                                         self.pod_group_ids(pods), req, max_pods_per_node)
         return self._results(table, idx, score, status)
