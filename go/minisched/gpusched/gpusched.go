@@ -862,6 +862,126 @@ func (x *Ctx) ScheduleSequentialClassesDevice(p int, dPodDigit, dPodTol, dGroup,
 	return nil
 }
 
+// ---- preferred node affinity and PreferNoSchedule scores (ABI v8, additive) ----
+//
+// Per (pod class, node) the caller gives A, the summed weights of the class's matching preferred node affinity
+// terms, and T, the number of the node's PreferNoSchedule taints the class does not tolerate; the library
+// normalises both per pod over its feasible nodes and adds wAffinity*na + wTaint*nt to the total
+// (include/minisched_hip.h, "Preferred node affinity and PreferNoSchedule scores").
+
+func toU16(v []uint16) *C.uint16_t {
+	if len(v) == 0 {
+		return nil
+	}
+	return (*C.uint16_t)(unsafe.Pointer(&v[0]))
+}
+
+// UploadNodeClassPrefs sets the preference column for nClasses classes over n nodes: affinity and taints hold
+// nClasses*n values each, class-major in List order; either may be nil (all zero).
+func (x *Ctx) UploadNodeClassPrefs(n, nClasses int, affinity, taints []uint16) error {
+	if (affinity != nil && len(affinity) != n*nClasses) || (taints != nil && len(taints) != n*nClasses) {
+		return errors.New("gpusched: affinity and taints hold nClasses*n values")
+	}
+	if rc := C.msh_upload_node_class_prefs(x.c, C.int32_t(n), C.int32_t(nClasses), toU16(affinity), toU16(taints)); rc != C.MSH_OK {
+		return x.lastErr("msh_upload_node_class_prefs", rc)
+	}
+	return nil
+}
+
+// PatchNodeClassPrefs replaces the values of the nodes at idx for every class: nClasses*len(idx) values each,
+// class-major; a nil slice writes zeros.
+func (x *Ctx) PatchNodeClassPrefs(idx []int32, affinity, taints []uint16) error {
+	if rc := C.msh_patch_node_class_prefs(x.c, C.int32_t(len(idx)), ptrI32(toI32(idx)), toU16(affinity), toU16(taints)); rc != C.MSH_OK {
+		return x.lastErr("msh_patch_node_class_prefs", rc)
+	}
+	return nil
+}
+
+// ClearNodeClassPrefs goes back to "no column".
+func (x *Ctx) ClearNodeClassPrefs() error {
+	if rc := C.msh_clear_node_class_prefs(x.c); rc != C.MSH_OK {
+		return x.lastErr("msh_clear_node_class_prefs", rc)
+	}
+	return nil
+}
+
+// NodeClassPrefs returns the number of classes and the two columns (nClasses*n values each, n the uploaded node
+// count), or 0 and nil when none is present.
+func (x *Ctx) NodeClassPrefs(n int) (nClasses int, affinity, taints []uint16, err error) {
+	var present, nc C.int32_t
+	if rc := C.msh_node_class_prefs(x.c, &nc, nil, nil, &present); rc != C.MSH_OK {
+		return 0, nil, nil, x.lastErr("msh_node_class_prefs", rc)
+	}
+	if present == 0 {
+		return 0, nil, nil, nil
+	}
+	affinity, taints = make([]uint16, int(nc)*n), make([]uint16, int(nc)*n)
+	if rc := C.msh_node_class_prefs(x.c, &nc, toU16(affinity), toU16(taints), &present); rc != C.MSH_OK {
+		return 0, nil, nil, x.lastErr("msh_node_class_prefs", rc)
+	}
+	return int(nc), affinity, taints, nil
+}
+
+// SetPreferenceWeights sets the two plugin weights, each in [0, 100]; 0 / 0 (the default) turns the scores off.
+func (x *Ctx) SetPreferenceWeights(wAffinity, wTaint int) error {
+	if rc := C.msh_set_preference_weights(x.c, C.int32_t(wAffinity), C.int32_t(wTaint)); rc != C.MSH_OK {
+		return x.lastErr("msh_set_preference_weights", rc)
+	}
+	return nil
+}
+
+// PreferenceWeights returns the two plugin weights.
+func (x *Ctx) PreferenceWeights() (wAffinity, wTaint int, err error) {
+	var a, t C.int32_t
+	if rc := C.msh_preference_weights(x.c, &a, &t); rc != C.MSH_OK {
+		return 0, 0, x.lastErr("msh_preference_weights", rc)
+	}
+	return int(a), int(t), nil
+}
+
+// SeqPrefsMaxNodes returns the largest table ScheduleSequentialPrefs takes with nres resources.
+func (x *Ctx) SeqPrefsMaxNodes(nres int) (int, error) {
+	var out C.int32_t
+	if rc := C.msh_seq_prefs_max_nodes(x.c, C.int32_t(nres), &out); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_seq_prefs_max_nodes", rc)
+	}
+	return int(out), nil
+}
+
+// ScheduleSequentialPrefs is ScheduleSequentialClasses with the two preference scores added to every feasible
+// node's total; with both weights 0 it is ScheduleSequentialClasses.
+func (x *Ctx) ScheduleSequentialPrefs(pods []*v1.Pod, b *HostBatch, group, class []int32, nres int, req []int64,
+	maxPodsPerNode int32) ([]Result, error) {
+	if !x.hasNodes {
+		return nil, errors.New("gpusched: UploadNodes has not been called")
+	}
+	p := len(pods)
+	if len(req) != nres*p || (group != nil && len(group) != p) || (class != nil && len(class) != p) {
+		return nil, errors.New("gpusched: req holds nres*len(pods) values, group and class len(pods)")
+	}
+	if err := x.pack(b, pods); err != nil {
+		return nil, err
+	}
+	if rc := C.msh_schedule_sequential_prefs(x.c, C.int32_t(p), ptrI8(b.pd[:p]), ptrU8(b.pt[:p]), ptrI32(toI32(group)),
+		ptrI32(toI32(class)), C.int32_t(nres), ptrI64(toI64(req)), C.int32_t(maxPodsPerNode), ptrI32(b.idx[:p]),
+		ptrI64(b.score[:p]), ptrI32(b.status[:p]), nil, nil); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_schedule_sequential_prefs", rc)
+	}
+	return x.results(b), nil
+}
+
+// ScheduleSequentialPrefsDevice is the asynchronous form over device pointers (msh_schedule_sequential_prefs_device);
+// as ScheduleSequentialClassesDevice.
+func (x *Ctx) ScheduleSequentialPrefsDevice(p int, dPodDigit, dPodTol, dGroup, dClass unsafe.Pointer, nres int,
+	dReq unsafe.Pointer, maxPodsPerNode int32, dIdx, dScore, dStatus, stream unsafe.Pointer) error {
+	if rc := C.msh_schedule_sequential_prefs_device(x.c, C.int32_t(p), (*C.int8_t)(dPodDigit), (*C.uint8_t)(dPodTol),
+		(*C.int32_t)(dGroup), (*C.int32_t)(dClass), C.int32_t(nres), (*C.int64_t)(dReq), C.int32_t(maxPodsPerNode),
+		(*C.int32_t)(dIdx), (*C.int64_t)(dScore), (*C.int32_t)(dStatus), stream); rc != C.MSH_OK {
+		return x.lastErr("msh_schedule_sequential_prefs_device", rc)
+	}
+	return nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

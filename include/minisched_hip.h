@@ -610,6 +610,61 @@ int msh_schedule_sequential_classes_device(msh_ctx* ctx, int32_t p, const int8_t
                                            int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
                                            int32_t* d_out_status, void* stream);
 
+/* Preferred node affinity and PreferNoSchedule scores (the scoring halves of upstream's NodeAffinity and
+ * TaintToleration, v1.22: nodeaffinity/node_affinity.go Score / NormalizeScore, tainttoleration/taint_toleration.go
+ * Score / NormalizeScore; additive in ABI 8). Two raw values per (pod class, node), static as the class masks are:
+ *   A[c][i]: the summed weights of the class's preferredDuringSchedulingIgnoredDuringExecution terms that match node i;
+ *   T[c][i]: the number of node i's PreferNoSchedule taints that the class does not tolerate.
+ * Their normalisation is not static: upstream normalises over the pod's feasible nodes, which change with every
+ * commit, so the kernel takes both maxima per pod.
+ * The column. affinity and taints are [C][n], class-major, nodes in List order, 1 <= C <= MSH_MAX_POD_CLASSES;
+ *   either may be NULL (all zero). n different from the uploaded node count is MSH_ERR_INVALID, a call before
+ *   msh_upload_nodes MSH_ERR_STATE.
+ * Lifetime and ordering are the class masks'. msh_upload_nodes drops the column; msh_patch_nodes, the count, capacity,
+ *   resource, zone and class-mask writers and the count resets keep it. The writers and the reader are synchronous
+ *   and ordered after the ctx's sequential launches in flight. msh_patch_node_class_prefs replaces the values of
+ *   nodes idx[k] for every class (arrays [C][count]; a NULL array writes zeros; indices pairwise distinct and in
+ *   range; with no column MSH_ERR_STATE). msh_clear_node_class_prefs returns to "no column". msh_node_class_prefs
+ *   reports *out_present, and with a column *out_C and the two [C][n] arrays (each may be NULL).
+ * The class space is shared with the class masks: when both columns are present at a call their C must be equal,
+ *   else MSH_ERR_STATE. A preference column without class masks means every node admits every class; class masks
+ *   without a preference column mean A = T = 0.
+ * msh_set_preference_weights: the plugin weights w_affinity and w_taint, each in [0, 100] (else MSH_ERR_INVALID),
+ *   default 0 / 0.
+ * msh_schedule_sequential_prefs / _prefs_device take msh_schedule_sequential_classes' arguments and contract. Per
+ *   pod, with F its feasible set exactly as _classes defines it:
+ *     maxA = max over F of A; na_i = 0 if maxA == 0, else floor(100 * A_i / maxA);
+ *     maxT = max over F of T; nt_i = 100 if maxT == 0, else 100 - floor(100 * T_i / maxT);
+ *     total_i = _classes's total_i + w_affinity * na_i + w_taint * nt_i,
+ *   the first maximum in List order wins and out_score is that total. A pod of class -1, and every pod when no
+ *   preference column is present, has A = T = 0: na = 0 and nt = 100 on every node, so out_score still carries
+ *   w_taint * 100. The status order and the commit are _classes's.
+ *   With both weights 0 the call is _classes itself, bit for bit, the same kernel instance.
+ *   Resource score mode NONE is allowed (the resource term is 0; nres may be 0).
+ * Refusals are _classes's, in its order (the class masks are not required by themselves), then: pod_class non-NULL
+ *   with neither column present, or both with unequal C: MSH_ERR_STATE; 100 * (W_res + w_affinity + w_taint) > 65,534,
+ *   W_res the resource score's plugin weight (0 in mode NONE): MSH_ERR_UNSUPPORTED (the packed key cannot hold the
+ *   sum). The device form treats every class value outside [0, C) as -1.
+ * Node limits: msh_seq_prefs_max_nodes, 4,096 nodes up to two resources and 2,048 above, in every score mode.
+ * Every other entry point ignores the column and the weights. A failed call changes nothing. */
+int msh_upload_node_class_prefs(msh_ctx* ctx, int32_t n, int32_t C, const uint16_t* affinity, const uint16_t* taints);
+int msh_patch_node_class_prefs(msh_ctx* ctx, int32_t count, const int32_t* idx, const uint16_t* affinity,
+                               const uint16_t* taints);
+int msh_clear_node_class_prefs(msh_ctx* ctx);
+int msh_node_class_prefs(msh_ctx* ctx, int32_t* out_C, uint16_t* out_affinity, uint16_t* out_taints,
+                         int32_t* out_present);
+int msh_set_preference_weights(msh_ctx* ctx, int32_t w_affinity, int32_t w_taint);
+int msh_preference_weights(const msh_ctx* ctx, int32_t* out_w_affinity, int32_t* out_w_taint);
+int msh_seq_prefs_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t* out_max_nodes);
+int msh_schedule_sequential_prefs(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                  const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                  const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                  int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_prefs_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                         const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
+                                         const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
+                                         int64_t* d_out_score, int32_t* d_out_status, void* stream);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

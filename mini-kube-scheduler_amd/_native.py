@@ -84,6 +84,9 @@ EXPORTED = (
     "msh_schedule_sequential_spread_scored_device",
     "msh_upload_node_class_bits", "msh_patch_node_class_bits", "msh_clear_node_class_bits", "msh_node_class_bits",
     "msh_seq_classes_max_nodes", "msh_schedule_sequential_classes", "msh_schedule_sequential_classes_device",
+    "msh_upload_node_class_prefs", "msh_patch_node_class_prefs", "msh_clear_node_class_prefs", "msh_node_class_prefs",
+    "msh_set_preference_weights", "msh_preference_weights", "msh_seq_prefs_max_nodes",
+    "msh_schedule_sequential_prefs", "msh_schedule_sequential_prefs_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -222,6 +225,15 @@ _SIGS = {
     "msh_seq_classes_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_schedule_sequential_classes": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
     "msh_schedule_sequential_classes_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "msh_upload_node_class_prefs": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "msh_patch_node_class_prefs": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "msh_clear_node_class_prefs": (C.c_int, [_P]),
+    "msh_node_class_prefs": (C.c_int, [_P, C.POINTER(_I32), _P, _P, C.POINTER(_I32)]),
+    "msh_set_preference_weights": (C.c_int, [_P, _I32, _I32]),
+    "msh_preference_weights": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32)]),
+    "msh_seq_prefs_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
+    "msh_schedule_sequential_prefs": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_prefs_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

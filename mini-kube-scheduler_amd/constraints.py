@@ -166,6 +166,62 @@ def node_admits(pod: Any, node: Any) -> bool:
             and tolerates_node_taints(pod, node))
 
 
+_PREFERRED = ("affinity", "nodeAffinity", "preferredDuringSchedulingIgnoredDuringExecution")
+
+
+def pod_preferred_terms(p: Any) -> list:
+    """The preferred node affinity's terms, each with `weight` and `preference` (a NodeSelectorTerm); empty without
+    one. Attribute objects give node_affinity_preferred."""
+    if hasattr(p, "node_affinity_preferred"):
+        return list(p.node_affinity_preferred or ())
+    return list(_get(p, "spec", *_PREFERRED, default=()) or ())
+
+
+def _term_matches(term: Any, labels: Mapping[str, str], name: str) -> bool | None:
+    """One NodeSelectorTerm against a node, by matches_node_affinity's rules; None for a term with neither
+    matchExpressions nor matchFields."""
+    exprs = list(_get(term, "matchExpressions", default=()) or ())
+    fields = list(_get(term, "matchFields", default=()) or ())
+    if not exprs and not fields:
+        return None
+    return all(_expression_matches(e, labels) for e in exprs) and all(_field_matches(f, name) for f in fields)
+
+
+def preferred_affinity_score(pod: Any, node: Any) -> int:
+    """pkg/scheduler/framework/plugins/nodeaffinity/node_affinity.go: Score, with
+    component-helpers/scheduling/corev1/nodeaffinity/nodeaffinity.go: NewPreferredSchedulingTerms and
+    PreferredSchedulingTerms.Score. The sum of `weight` over the preferred terms whose `preference` matches the node;
+    a term of weight 0, or whose preference has neither matchExpressions nor matchFields, is skipped."""
+    labels, name = node_labels(node), node_name(node)
+    total = 0
+    for t in pod_preferred_terms(pod):
+        w = int(_get(t, "weight", default=0) or 0)
+        if w == 0:
+            continue
+        if _term_matches(_get(t, "preference", default={}) or {}, labels, name):
+            total += w
+    return total
+
+
+def prefer_no_schedule_count(pod: Any, node: Any) -> int:
+    """pkg/scheduler/framework/plugins/tainttoleration/taint_toleration.go: Score, with
+    getAllTolerationPreferNoSchedule and countIntolerableTaintsPreferNoSchedule. The node's taints of effect
+    PreferNoSchedule that none of the pod's tolerations with an empty effect or effect PreferNoSchedule tolerates."""
+    tols = [t for t in pod_tolerations(pod) if _tol_field(t, "effect") in ("", "PreferNoSchedule")]
+    return sum(1 for taint in node_taints(node)
+               if _tol_field(taint, "effect") == "PreferNoSchedule"
+               and not any(toleration_tolerates_taint(t, taint) for t in tols))
+
+
+def preference_key(pod: Any) -> str:
+    """The canonical form of what preferred_affinity_score and prefer_no_schedule_count read from a pod: the
+    preferred terms in order, and the tolerations as class_key reduces them. Pods with equal keys get equal raw
+    values on every node."""
+    tols = sorted([_tol_field(t, "key"), _tol_field(t, "operator", "op"), _tol_field(t, "value"),
+                   _tol_field(t, "effect")] for t in pod_tolerations(pod))
+    return json.dumps([_plain(pod_preferred_terms(pod)), tols], sort_keys=True)
+
+
 def _plain(x: Any) -> Any:
     """A JSON-able copy of the public fields of x (dicts, sequences, attribute objects)."""
     if isinstance(x, Mapping):

@@ -417,6 +417,11 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
     c->have_class = false;  // and the class masks
     c->h_class.clear();
     c->n_classes = 0;
+    c->have_prefs = false;  // and the preference values
+    c->pref_classes = 0;
+    c->h_pref_a.clear();
+    c->h_pref_t.clear();
+    c->pref_dirty = true;
   }
   c->cur = s;
   c->n_nodes = n;
@@ -806,6 +811,7 @@ void msh_destroy(msh_ctx* c) {
   (void)hipFree(c->d_used);
   (void)hipFree(c->d_zone);
   (void)hipFree(c->d_class);
+  (void)hipFree(c->d_pref);
   (void)hipFree(c->d_skew);
   (void)hipFree(c->d_spread_cnt);
   for (hipEvent_t e : c->async_ev)
@@ -2099,6 +2105,7 @@ int class_reserve(msh_ctx* c) {
   c->d_class = d;
   c->class_cap = (size_t)c->n_pad;
   c->have_class = false;  // the old column went with its buffer
+  c->pref_dirty = true;
   c->h_class.clear();
   c->n_classes = 0;
   return MSH_OK;
@@ -2139,6 +2146,7 @@ int msh_upload_node_class_bits(msh_ctx* c, int32_t n, int32_t C, const uint64_t*
   if (rc != MSH_OK) return rc;
   std::vector<uint64_t> h(bits, bits + n);
   c->have_class = false;  // a failed copy leaves no column
+  c->pref_dirty = true;   // the preference table holds the masks' verdicts
   if ((rc = class_write_all(c, h.data())) != MSH_OK) return rc;
   c->h_class.swap(h);
   c->n_classes = C;
@@ -2168,6 +2176,7 @@ int msh_patch_node_class_bits(msh_ctx* c, int32_t count, const int32_t* idx, con
   // the patched column whole: 64 KB at the largest table a class call takes, one copy
   std::vector<uint64_t> h(c->h_class);
   for (int32_t k = 0; k < count; ++k) h[(size_t)idx[k]] = bits[k];
+  c->pref_dirty = true;
   int rc = class_write_all(c, h.data());
   if (rc != MSH_OK) {
     c->have_class = false;  // the device column is in an unknown state
@@ -2181,6 +2190,7 @@ int msh_clear_node_class_bits(msh_ctx* c) {
   if (!c) return MSH_ERR_INVALID;
   c->err.clear();
   c->have_class = false;  // launches in flight keep reading the device column, which stays allocated
+  c->pref_dirty = true;
   c->h_class.clear();
   c->n_classes = 0;
   return MSH_OK;
@@ -2337,6 +2347,314 @@ int msh_schedule_sequential_classes(msh_ctx* c, int32_t p, const int8_t* pod_dig
   rc = classes_device(c, entry, p, io.d_pd, io.d_pt, pod_group ? sg : nullptr, pod_class ? sc : nullptr, nres,
                       reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
                       io.o_status, c->stream);
+  if (rc != MSH_OK) return rc;
+  if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
+  if (commit_cb)
+    for (int32_t j = 0; j < p; j++)
+      if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
+  return MSH_OK;
+}
+
+// The per-class preference values (msh_schedule_sequential_prefs). The host copies are the column; the device table
+// the kernel reads is derived from them and from the class masks by the first call after either changed
+// (prefs_table), so the writers touch no device memory and cannot leave the device in an unknown state.
+namespace {
+void prefs_drop(msh_ctx* c) {
+  c->have_prefs = false;
+  c->pref_classes = 0;
+  c->h_pref_a.clear();
+  c->h_pref_t.clear();
+  c->pref_dirty = true;
+}
+
+// The device table for the ctx's columns and a kernel of npl nodes per thread (msh::PrefArgs::rows): classes x
+// PREF_THREADS records of 2 * npl dwords. Ordered after the sequential launches in flight, which read the old one
+// until they end; synchronous.
+int prefs_table(msh_ctx* c, int32_t npl) {
+  const int32_t C = c->have_prefs ? c->pref_classes : (c->have_class ? c->n_classes : 0);
+  if (!c->pref_dirty && c->pref_dev_classes == C && c->pref_stride == 2 * npl) return MSH_OK;
+  const size_t rec = 2 * (size_t)npl, per_class = rec * msh::PREF_THREADS, total = per_class * (size_t)C;
+  std::vector<uint32_t> h(total, 0u);
+  uint64_t am = 0, tm = 0;
+  const size_t n = (size_t)c->n_nodes;
+  for (int32_t k = 0; k < C; ++k) {
+    uint32_t* row = h.data() + per_class * (size_t)k;
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t av = c->have_prefs && !c->h_pref_a.empty() ? c->h_pref_a[(size_t)k * n + i] : 0u;
+      const uint32_t tv = c->have_prefs && !c->h_pref_t.empty() ? c->h_pref_t[(size_t)k * n + i] : 0u;
+      const bool admits = !c->have_class || ((c->h_class[i] >> k) & 1ull) != 0;
+      uint32_t* r = row + (i / (size_t)npl) * rec;
+      r[i % (size_t)npl] = av | (tv << 16);
+      r[npl] |= (admits ? 1u : 0u) << (i % (size_t)npl);
+      if (av) am |= 1ull << k;
+      if (tv) tm |= 1ull << k;
+    }
+  }
+  wait_events(c->seq_inflight);
+  if (total > c->pref_cap) {
+    uint32_t* d = nullptr;
+    MSH_HIP(c, hipMalloc(&d, total * sizeof(uint32_t)));
+    (void)hipFree(c->d_pref);
+    c->d_pref = d;
+    c->pref_cap = total;
+    c->pref_dirty = true;  // the old table went with its buffer
+  }
+  if (total) MSH_HIP(c, hipMemcpy(c->d_pref, h.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
+  c->pref_dev_classes = C;
+  c->pref_stride = 2 * npl;
+  c->pref_amask = am;
+  c->pref_tmask = tm;
+  c->pref_dirty = false;
+  return MSH_OK;
+}
+}  // namespace
+
+int msh_upload_node_class_prefs(msh_ctx* c, int32_t n, int32_t C, const uint16_t* affinity, const uint16_t* taints) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (n != c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "preference column of " + std::to_string(n) + " entries per class for " +
+                                        std::to_string(c->n_nodes) + " uploaded nodes");
+  if (C < 1 || C > MSH_MAX_POD_CLASSES) return fail(c, MSH_ERR_INVALID, "C outside [1, MSH_MAX_POD_CLASSES]");
+  const size_t len = (size_t)C * (size_t)n;
+  std::vector<uint16_t> a, t;  // an absent array stays empty: all zero
+  if (affinity) a.assign(affinity, affinity + len);
+  if (taints) t.assign(taints, taints + len);
+  c->h_pref_a.swap(a);
+  c->h_pref_t.swap(t);
+  c->pref_classes = C;
+  c->have_prefs = true;
+  c->pref_dirty = true;
+  return MSH_OK;
+}
+
+int msh_patch_node_class_prefs(msh_ctx* c, int32_t count, const int32_t* idx, const uint16_t* affinity,
+                               const uint16_t* taints) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (!c->have_prefs) return fail(c, MSH_ERR_STATE, "msh_upload_node_class_prefs has not been called");
+  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
+  if (count == 0) return MSH_OK;
+  if (!idx) return fail(c, MSH_ERR_INVALID, "null patch indices");
+  std::vector<int32_t> sorted(idx, idx + count);
+  std::sort(sorted.begin(), sorted.end());
+  if (sorted.front() < 0 || sorted.back() >= c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "patch index outside [0, n)");
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return fail(c, MSH_ERR_INVALID, "duplicate patch index");
+  const size_t n = (size_t)c->n_nodes, C = (size_t)c->pref_classes;
+  auto apply = [&](std::vector<uint16_t>& col, const uint16_t* v) {  // a null array writes zeros
+    if (col.empty() && !v) return;
+    if (col.empty()) col.assign(C * n, 0);
+    for (size_t k = 0; k < C; ++k)
+      for (int32_t e = 0; e < count; ++e) col[k * n + (size_t)idx[e]] = v ? v[k * (size_t)count + (size_t)e] : 0;
+  };
+  apply(c->h_pref_a, affinity);
+  apply(c->h_pref_t, taints);
+  c->pref_dirty = true;
+  return MSH_OK;
+}
+
+int msh_clear_node_class_prefs(msh_ctx* c) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  prefs_drop(c);  // launches in flight keep reading the device table, which stays allocated
+  return MSH_OK;
+}
+
+int msh_node_class_prefs(msh_ctx* c, int32_t* out_C, uint16_t* out_affinity, uint16_t* out_taints,
+                         int32_t* out_present) {
+  if (!c || !out_present) return MSH_ERR_INVALID;
+  c->err.clear();
+  *out_present = c->have_prefs ? 1 : 0;
+  if (out_C) *out_C = c->have_prefs ? c->pref_classes : 0;
+  if (!c->have_prefs) return MSH_OK;
+  const size_t len = (size_t)c->pref_classes * (size_t)c->n_nodes;
+  auto give = [&](const std::vector<uint16_t>& col, uint16_t* out) {
+    if (!out) return;
+    if (col.empty()) std::fill(out, out + len, (uint16_t)0);
+    else std::copy(col.begin(), col.end(), out);
+  };
+  give(c->h_pref_a, out_affinity);
+  give(c->h_pref_t, out_taints);
+  return MSH_OK;
+}
+
+int msh_set_preference_weights(msh_ctx* c, int32_t w_affinity, int32_t w_taint) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (w_affinity < 0 || w_affinity > 100 || w_taint < 0 || w_taint > 100)
+    return fail(c, MSH_ERR_INVALID, "preference weight outside [0, 100]");
+  c->w_aff = w_affinity;
+  c->w_taint = w_taint;
+  return MSH_OK;
+}
+
+int msh_preference_weights(const msh_ctx* c, int32_t* out_w_affinity, int32_t* out_w_taint) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_w_affinity) *out_w_affinity = c->w_aff;
+  if (out_w_taint) *out_w_taint = c->w_taint;
+  return MSH_OK;
+}
+
+int msh_seq_prefs_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = msh::seq_prefs_max_nodes(nres);
+  return MSH_OK;
+}
+
+namespace {
+// the classes of a prefs call: the columns' common C (0 without a column)
+int32_t prefs_classes(const msh_ctx* c) { return c->have_prefs ? c->pref_classes : (c->have_class ? c->n_classes : 0); }
+
+// What a prefs call with a nonzero weight needs, checked before any device work: _classes's refusals in its order
+// (the class column is not required by itself), with the preference kernel's table limits, then the two of this
+// call: pod classes with neither column (and columns of unequal C), and a weighted sum the packed key cannot hold.
+int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node, bool grouped,
+                bool classed) {
+  if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
+  if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
+  int rc = refuse_random(c, entry);
+  if (rc != MSH_OK) return rc;
+  if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (grouped && !c->have_zone) return fail(c, MSH_ERR_STATE, "msh_upload_node_zones has not been called");
+  if (nres) {
+    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+    if (nres != c->nres)
+      return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
+                                          std::to_string(c->nres));
+  }
+  if (scored) {
+    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+    if (nres != c->rs_nres)
+      return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
+                                        " resources, the call has " + std::to_string(nres));
+  }
+  const int32_t lim = msh::seq_prefs_max_nodes(nres);
+  if (c->n_nodes > lim) return fail(c, MSH_ERR_UNSUPPORTED, msh::seq_table_limit_message("preference", lim, nres));
+  if (scored && c->res_max > MSH_RESOURCE_SCORE_MAX)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
+                "or patch wrote " + std::to_string(c->res_max));
+  if (classed && !c->have_class && !c->have_prefs)
+    return fail(c, MSH_ERR_STATE, "pod classes with neither msh_upload_node_class_prefs nor msh_upload_node_class_bits");
+  if (classed && c->have_class && c->have_prefs && c->n_classes != c->pref_classes)
+    return fail(c, MSH_ERR_STATE, "the class masks were uploaded for C = " + std::to_string(c->n_classes) +
+                                      ", the preference values for C = " + std::to_string(c->pref_classes));
+  const int64_t wsum = (scored ? c->rs_weight : 0) + c->w_aff + c->w_taint;
+  if (100 * wsum > 65534)
+    return fail(c, MSH_ERR_UNSUPPORTED, "the weights of the resource score and the two preference scores sum to " +
+                                            std::to_string(wsum) + ": the packed key holds 100 x 655 at most");
+  return MSH_OK;
+}
+
+int prefs_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                 const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
+                 int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
+                 void* stream) {
+  c->err.clear();
+  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // group, class and score optional
+    return fail(c, MSH_ERR_INVALID, "null device pointer");
+  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
+  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr);
+  if (rc != MSH_OK) return rc;
+  if (p == 0) return MSH_OK;
+  DeviceGuard g(c->device);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+  if (d_pod_class && (rc = prefs_table(c, msh::seq_prefs_npl(nres))) != MSH_OK) return rc;
+  msh::PrefArgs pa{};
+  pa.ss.s = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
+                        d_out_score, d_out_status);
+  if (scored) spread_score_setting(c, nres, pa.ss);  // else weight 0, every resource weight 0 and the magic 0: rs = 0
+  pa.rows = d_pod_class ? c->d_pref : nullptr;
+  pa.pod_class = d_pod_class;
+  pa.n_classes = d_pod_class ? c->pref_dev_classes : 0;
+  pa.amask = d_pod_class ? c->pref_amask : 0;
+  pa.tmask = d_pod_class ? c->pref_tmask : 0;
+  pa.w_aff = (uint32_t)c->w_aff;
+  pa.w_taint = (uint32_t)c->w_taint;
+  // one sequential launch of a ctx at a time (seq_device): each commits into the same counts
+  for (auto& ev : c->seq_inflight)
+    if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
+  std::string err;
+  hipError_t e;
+  {
+    TimedLaunch tl(c);
+    e = msh::launch_seq_prefs(pa, s, &err);
+  }
+  if (e != hipSuccess) {
+    if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
+    return hip_fail(c, e, "seq_prefs_kernel");
+  }
+  c->counts_dirty = false;  // the one workgroup folded the replicas
+  return track_launch(c, s, true);
+}
+}  // namespace
+
+int msh_schedule_sequential_prefs_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                         const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
+                                         const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
+                                         int64_t* d_out_score, int32_t* d_out_status, void* stream) {
+  if (!c) return MSH_ERR_INVALID;
+  if (c->w_aff == 0 && c->w_taint == 0)  // nothing to add: _classes itself, its kernel instance
+    return classes_device(c, "msh_schedule_sequential_prefs_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
+                          nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+  return prefs_device(c, "msh_schedule_sequential_prefs_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
+                      nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+}
+
+int msh_schedule_sequential_prefs(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                  const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                  const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                  int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  const char* entry = "msh_schedule_sequential_prefs";
+  if (!c) return MSH_ERR_INVALID;
+  if (c->w_aff == 0 && c->w_taint == 0)  // nothing to add: _classes itself
+    return msh_schedule_sequential_classes(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
+                                           max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+  c->err.clear();
+  if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // group, class and score optional
+    return fail(c, MSH_ERR_INVALID, "null host pointer");
+  if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
+  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr);
+  if (rc != MSH_OK) return rc;
+  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
+  const int32_t C = prefs_classes(c);
+  for (int32_t j = 0; pod_group && j < p; ++j)
+    if (pod_group[j] < -1 || pod_group[j] >= c->sp_groups)
+      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": group " + std::to_string(pod_group[j]) +
+                                          " outside [-1, G) with G = " + std::to_string(c->sp_groups));
+  for (int32_t j = 0; pod_class && j < p; ++j)
+    if (pod_class[j] < -1 || pod_class[j] >= C)
+      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": class " + std::to_string(pod_class[j]) +
+                                          " outside [-1, C) with C = " + std::to_string(C));
+  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
+    if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
+      return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
+    if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
+      return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
+                                          std::to_string(e % (size_t)p));
+  }
+  if (p == 0) return MSH_OK;
+  DeviceGuard g(c->device);
+  HostIO io;
+  if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
+  // the requests, groups and classes through the page-locked node stage, which the kernel reads itself (spread_host)
+  const size_t rbytes = (size_t)nres * (size_t)p * sizeof(int64_t), cbytes = (size_t)p * sizeof(int32_t);
+  if ((rc = node_stage(c, rbytes + 2 * cbytes)) != MSH_OK) return rc;
+  if (rbytes) std::memcpy(c->h_nstage, pod_req, rbytes);
+  int32_t* sg = reinterpret_cast<int32_t*>(c->h_nstage + rbytes);
+  int32_t* sc = reinterpret_cast<int32_t*>(c->h_nstage + rbytes + cbytes);
+  if (pod_group) std::memcpy(sg, pod_group, cbytes);
+  if (pod_class) std::memcpy(sc, pod_class, cbytes);
+  rc = prefs_device(c, entry, p, io.d_pd, io.d_pt, pod_group ? sg : nullptr, pod_class ? sc : nullptr, nres,
+                    reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
+                    io.o_status, c->stream);
   if (rc != MSH_OK) return rc;
   if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
   if (commit_cb)

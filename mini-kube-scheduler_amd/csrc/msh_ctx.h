@@ -124,6 +124,21 @@ struct msh_ctx {
   bool have_class = false;
   int32_t n_classes = 0;
   std::vector<uint64_t> h_class;
+  // the per-class preference values (msh_upload_node_class_prefs): the host copies, [pref_classes][n_nodes] each (what
+  // msh_node_class_prefs returns), and the weights of msh_set_preference_weights; dropped by msh_upload_nodes. The
+  // device table that msh_schedule_sequential_prefs reads is derived from them and from the class masks (rows A | T
+  // << 16 of pref_stride dwords, then the admit bits, pref_dev_classes classes) and rebuilt by the first call after
+  // either column changed (pref_dirty); pref_amask / pref_tmask: the classes with a nonzero A / T on some node.
+  bool have_prefs = false;
+  int32_t pref_classes = 0;
+  std::vector<uint16_t> h_pref_a, h_pref_t;
+  int32_t w_aff = 0, w_taint = 0;
+  uint32_t* d_pref = nullptr;
+  size_t pref_cap = 0;  // dwords
+  bool pref_dirty = true;
+  int32_t pref_dev_classes = 0;
+  int64_t pref_stride = 0;
+  uint64_t pref_amask = 0, pref_tmask = 0;
   // per caller stream, the event of its last sequential launch: an alias of a table version's reader
   // event (not owned here; track_launch)
   std::vector<std::pair<hipStream_t, hipEvent_t>> seq_inflight;

@@ -352,6 +352,27 @@ struct ClassArgs {
 // Nodes the class kernels hold: the topology-spread limits unscored, the scored topology-spread limits scored.
 int32_t seq_classes_max_nodes(int32_t nres, bool scored);
 hipError_t launch_seq_classes(const ClassArgs& a, bool scored, hipStream_t s, std::string* err);
+// The preference form (msh_seq_prefs.hip, msh_schedule_sequential_prefs with a nonzero preference weight): the
+// scored class form's feasible set and totals plus w_aff * na + w_taint * nt, the normalised preferred node affinity
+// and PreferNoSchedule scores, both normalised per pod over its feasible nodes. The class conjunct comes from
+// `admit`, not from a column of words. Resource score mode NONE: ss.weight 0, ss.rw all 0, ss.wsum_magic 0, and
+// ss.s.f.nres may be 0. 100 * (ss.weight + w_aff + w_taint) must be <= 65,534 (the packed key; checked on the host).
+constexpr int PREF_THREADS = 1024;  // the records of a class in the device table: one per thread of the largest instance
+struct PrefArgs {
+  SpreadScoreArgs ss;
+  // [n_classes][PREF_THREADS] records of 2 * npl dwords, npl = seq_prefs_npl(ss.s.f.nres): record t holds
+  // A | T << 16 of nodes t * npl .. t * npl + npl - 1, then their admit bits in one dword (bit k: node t * npl + k
+  // admits the class), then padding; slots past the table 0. 16-byte aligned, or null (no pod has a class)
+  const uint32_t* rows;
+  const int32_t* pod_class;  // [ss.s.f.s.n_pods]: any value outside [0, n_classes) is a pod without a class, or null
+  int32_t n_classes;         // 0..CLASS_MAX
+  uint64_t amask, tmask;     // bit c: class c has a nonzero A / T on some node
+  uint32_t w_aff, w_taint;   // the weights, [0, 100]
+};
+// Nodes the preference kernel holds: the scored limits in every resource score mode; and its nodes per thread.
+int32_t seq_prefs_max_nodes(int32_t nres);
+int32_t seq_prefs_npl(int32_t nres);
+hipError_t launch_seq_prefs(const PrefArgs& a, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

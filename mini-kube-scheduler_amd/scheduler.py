@@ -636,6 +636,104 @@ class DeviceContext:
             self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
             d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
 
+    # -- preferred node affinity and PreferNoSchedule scores: per-class raw values --
+    def _pref_array(self, a, n_classes: int, width: int, what: str) -> np.ndarray | None:
+        if a is None:
+            return None
+        v = np.asarray(a)
+        if v.shape != (n_classes, width) or (v.size and v.dtype.kind not in "iu"):
+            raise ValueError(f"{what}: an integer array shaped (n_classes, {width})")
+        if v.size and (int(v.min()) < 0 or int(v.max()) > 0xFFFF):
+            raise ValueError(f"{what}: values within uint16")
+        return np.ascontiguousarray(v, np.uint16)
+
+    def upload_node_class_prefs(self, n_classes: int, affinity=None, taints=None) -> None:
+        """msh_upload_node_class_prefs: the raw preferred-affinity sums and PreferNoSchedule counts, each shaped
+        (n_classes, n_nodes) in List order, or None (all zero). upload_nodes drops the column; every other writer keeps
+        it; only schedule_sequential_prefs reads it."""
+        a = self._pref_array(affinity, int(n_classes), self.n_nodes, "affinity")
+        t = self._pref_array(taints, int(n_classes), self.n_nodes, "taints")
+        self._check(self._lib.msh_upload_node_class_prefs(self.handle, self.n_nodes, int(n_classes), N.ptr(a), N.ptr(t)))
+
+    def patch_node_class_prefs(self, idx, affinity=None, taints=None) -> None:
+        """msh_patch_node_class_prefs: the values of nodes idx[k] for every class, each array shaped (n_classes,
+        len(idx)) or None (zeros)."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        col = self.node_class_prefs()
+        nc = col[0] if col is not None else 0
+        a = self._pref_array(affinity, nc, len(idx), "affinity") if col is not None else None
+        t = self._pref_array(taints, nc, len(idx), "taints") if col is not None else None
+        self._check(self._lib.msh_patch_node_class_prefs(self.handle, len(idx), N.ptr(idx), N.ptr(a), N.ptr(t)))
+
+    def clear_node_class_prefs(self) -> None:
+        """msh_clear_node_class_prefs: back to "no column"."""
+        self._check(self._lib.msh_clear_node_class_prefs(self.handle))
+
+    def node_class_prefs(self) -> tuple[int, np.ndarray, np.ndarray] | None:
+        """msh_node_class_prefs: (n_classes, affinity, taints), the arrays shaped (n_classes, n_nodes), or None when
+        no column is present."""
+        present, nc = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.msh_node_class_prefs(self.handle, C.byref(nc), None, None, C.byref(present)))
+        if not present.value:
+            return None
+        a = np.zeros((nc.value, self.n_nodes), np.uint16)
+        t = np.zeros((nc.value, self.n_nodes), np.uint16)
+        self._check(self._lib.msh_node_class_prefs(self.handle, C.byref(nc), N.ptr(a) if a.size else None,
+                                                   N.ptr(t) if t.size else None, C.byref(present)))
+        return nc.value, a, t
+
+    def set_preference_weights(self, affinity: int = 0, taint: int = 0) -> None:
+        """msh_set_preference_weights: the plugin weights of the two preference scores, each in [0, 100]."""
+        self._check(self._lib.msh_set_preference_weights(self.handle, int(affinity), int(taint)))
+
+    def preference_weights(self) -> tuple[int, int]:
+        a, t = C.c_int32(), C.c_int32()
+        self._check(self._lib.msh_preference_weights(self.handle, C.byref(a), C.byref(t)))
+        return a.value, t.value
+
+    def seq_prefs_max_nodes(self, nres: int = 0) -> int:
+        """msh_seq_prefs_max_nodes: the largest table schedule_sequential_prefs takes with nres (0..4) resources."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_prefs_max_nodes(self.handle, int(nres), C.byref(out)))
+        return out.value
+
+    def schedule_sequential_prefs(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_group=None, pod_class=None,
+                                  pod_req=None, max_pods_per_node: int = 0,
+                                  on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_prefs: schedule_sequential_classes with w_affinity * na + w_taint * nt added to
+        every feasible node's total, na and nt normalised per pod over its feasible nodes. With both weights 0 it is
+        schedule_sequential_classes."""
+        pod_digit = np.ascontiguousarray(pod_digit, np.int8)
+        pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
+        cols = [pod_digit, pod_tol]
+        if pod_group is not None:
+            pod_group = self._int32s(pod_group, "pod_group")
+            cols.append(pod_group)
+        if pod_class is not None:
+            pod_class = self._int32s(pod_class, "pod_class")
+            cols.append(pod_class)
+        p = _same_len("schedule_sequential_prefs", *cols)
+        nres = 0
+        if pod_req is not None:
+            pod_req = self._amounts(pod_req)
+            if pod_req.shape[1] != p:
+                raise ValueError("pod_req is shaped (nres, p)")
+            nres = pod_req.shape[0]
+        idx, score, status = self._outputs(p, out)
+        cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
+        self._check(self._lib.msh_schedule_sequential_prefs(
+            self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), N.ptr(pod_class), nres,
+            N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
+        return idx, score, status
+
+    def schedule_sequential_prefs_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
+                                         d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
+                                         d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
+        """msh_schedule_sequential_prefs_device (asynchronous on `stream`; as schedule_sequential_classes_device)."""
+        self._check(self._lib.msh_schedule_sequential_prefs_device(
+            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
+            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):
     # ctypes argument conversion cost ~0.9 us per call next to a ~2.6 us launch.
@@ -851,6 +949,13 @@ class Scheduler:
     constraints per node snapshot and, whenever some pod of the call has a class that some node does not admit,
     makes the class call (DeviceContext.schedule_sequential_classes) with whatever else is configured. A call
     whose pods are admitted everywhere is made exactly as before. schedule_batch ignores them.
+
+    The two preference scores are off by default. With preferred_affinity_weight or prefer_no_schedule_weight nonzero
+    (each in [0, 100]) a pod's class is keyed by its constraints and its preferences (constraints.class_key +
+    constraints.preference_key), a class gets an id if some node does not admit it or if one of its raw values
+    (constraints.preferred_affinity_score, constraints.prefer_no_schedule_count) is nonzero on some node, both
+    columns are uploaded for the same classes, and a call in which some pod has such a preference is made with
+    DeviceContext.schedule_sequential_prefs; every other call takes the paths above.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
@@ -859,8 +964,14 @@ class Scheduler:
                  device: int = 0, ctx: DeviceContext | None = None, *, tie_break="first", tie_seed: int = 0,
                  resources: Sequence[str] | None = None, resource_score=None, resource_score_weight: int = 1,
                  resource_weights=None, zones: str | None = None, spread_groups: Mapping[str, int] | None = None,
-                 spread_label: str = "app"):
+                 spread_label: str = "app", preferred_affinity_weight: int = 0, prefer_no_schedule_weight: int = 0):
         self.resources = None if resources is None else tuple(resources)
+        for w in (preferred_affinity_weight, prefer_no_schedule_weight):
+            if isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= 100:
+                raise ValueError("preferred_affinity_weight / prefer_no_schedule_weight: integers in [0, 100]")
+        self.preferred_affinity_weight = preferred_affinity_weight
+        self.prefer_no_schedule_weight = prefer_no_schedule_weight
+        self._prefs_on = bool(preferred_affinity_weight or prefer_no_schedule_weight)
         if (zones is None) != (spread_groups is None):
             raise ValueError("zones and spread_groups go together")
         if spread_groups is not None:
@@ -899,6 +1010,13 @@ class Scheduler:
         self._class_ids: dict[str, int] = {}
         self._class_masks: list[np.ndarray] = []  # per id, the nodes (List order) that admit the class
         self._class_synced = False  # the masks are on the device
+        # with a preference weight: per id, the raw preferred-affinity sums and PreferNoSchedule counts by node, and the
+        # ids with a nonzero raw value somewhere (constraints.preferred_affinity_score / prefer_no_schedule_count)
+        self._class_aff: list[np.ndarray] = []
+        self._class_pns: list[np.ndarray] = []
+        self._class_prefers: set[int] = set()
+        if self._prefs_on:
+            self.ctx.set_preference_weights(preferred_affinity_weight, prefer_no_schedule_weight)
         self._tainted: bool | None = None  # a node of the snapshot has a NoSchedule / NoExecute taint (None: not looked yet)
 
     @staticmethod
@@ -941,6 +1059,7 @@ class Scheduler:
         self._zone_synced = False
         self._node_objs = [nodes[i] for i in self.nodes.order]
         self._class_ids, self._class_masks, self._class_synced, self._tainted = {}, [], False, None
+        self._class_aff, self._class_pns, self._class_prefers = [], [], set()
         return self.nodes
 
     def _results(self, pods: PodTable, idx, score, status) -> list[ScheduleResult]:
@@ -1024,27 +1143,42 @@ class Scheduler:
         affinity, TaintToleration): pods with equal constraints.class_key share an id, ids persist for the node
         snapshot, and a class that every node admits is -1. More than MAX_POD_CLASSES classes that some node does
         not admit raise ValueError."""
+        effects = ("NoSchedule", "NoExecute", "PreferNoSchedule") if self._prefs_on else ("NoSchedule", "NoExecute")
         if self._tainted is None:
-            self._tainted = any(_tol_field(t, "effect") in ("NoSchedule", "NoExecute")
-                                for n in self._node_objs for t in K.node_taints(n))
+            self._tainted = any(_tol_field(t, "effect") in effects for n in self._node_objs for t in K.node_taints(n))
         out = np.full(len(pods), -1, np.int32)
+        n_nodes = len(self._node_objs)
         for j, p in enumerate(pods):
             # without taints the tolerations decide nothing: a pod with no other constraint needs no key
             if not self._tainted and not (K.pod_node_name(p) or K.pod_node_selector(p)
-                                          or K.pod_affinity_terms(p) is not None):
+                                          or K.pod_affinity_terms(p) is not None
+                                          or (self._prefs_on and K.pod_preferred_terms(p))):
                 continue
-            key = K.class_key(p)
+            key = K.class_key(p) + K.preference_key(p) if self._prefs_on else K.class_key(p)
             cid = self._class_ids.get(key)
             if cid is None:
-                mask = np.array([K.node_admits(p, n) for n in self._node_objs], bool).reshape(len(self._node_objs))
+                mask = np.array([K.node_admits(p, n) for n in self._node_objs], bool).reshape(n_nodes)
                 cid = -1
-                if not mask.all():
+                aff = pns = None
+                if self._prefs_on:  # with a preference weight a class with a nonzero raw value gets an id too
+                    aff = np.array([K.preferred_affinity_score(p, n) for n in self._node_objs], np.int64).reshape(n_nodes)
+                    pns = np.array([K.prefer_no_schedule_count(p, n) for n in self._node_objs], np.int64).reshape(n_nodes)
+                    if max(aff.max(initial=0), pns.max(initial=0)) > 0xFFFF:
+                        raise ValueError("a pod's summed preferred node affinity weights (or PreferNoSchedule taint "
+                                         "count) on one node exceed 65,535")
+                prefers = self._prefs_on and bool(aff.any() or pns.any())
+                if not mask.all() or prefers:
                     if len(self._class_masks) >= N.MAX_POD_CLASSES:
                         raise ValueError(f"more than {N.MAX_POD_CLASSES} classes of node constraints "
                                          f"(MAX_POD_CLASSES) against one node snapshot")
                     cid = len(self._class_masks)
                     self._class_masks.append(mask)
                     self._class_synced = False
+                    if self._prefs_on:
+                        self._class_aff.append(aff.astype(np.uint16))
+                        self._class_pns.append(pns.astype(np.uint16))
+                        if prefers:
+                            self._class_prefers.add(cid)
                 self._class_ids[key] = cid
             out[j] = cid
         return out
@@ -1075,8 +1209,15 @@ class Scheduler:
         req = self._sync_spread_inputs(pods)
         if not self._class_synced:
             self.ctx.upload_node_class_bits(len(self._class_masks), self.node_class_bits())
+            if self._prefs_on:  # both columns, for the same classes
+                self.ctx.upload_node_class_prefs(len(self._class_masks), np.array(self._class_aff, np.uint16),
+                                                 np.array(self._class_pns, np.uint16))
             self._class_synced = True
         groups = self.pod_group_ids(pods) if self.zones is not None else None
+        if self._class_prefers.intersection(int(c) for c in classes):  # some pod of the call has a preference
+            idx, score, status = self.ctx.schedule_sequential_prefs(table.digit, table.tolerates, groups, classes, req,
+                                                                    max_pods_per_node)
+            return self._results(table, idx, score, status)
         idx, score, status = self.ctx.schedule_sequential_classes(table.digit, table.tolerates, groups, classes, req,
                                                                   max_pods_per_node)
         return self._results(table, idx, score, status)
