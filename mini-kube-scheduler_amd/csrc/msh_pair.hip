@@ -354,11 +354,16 @@ __global__ __launch_bounds__(PAIR_WAVES * WAVE) void pair_kernel(PairArgsN<NB> a
 // Each wave evaluates PL_BPW = 2 64-pod blocks together: a group's planes are read from LDS once per
 // wave and applied to both, and the table copy is amortised over W x 2 blocks.
 // Per lane and 32-node word: xi = X & nT, dm' (4 v_bitop3), and per two words one AND3 into the
-// group's match flag, plus, KX, one OR of the feasible non-matches (dm' & ~xi): 5.5 VALU per word in
-// the identity-like modes, 6.5 with KX. The identity-like modes need no per-lane reduction beside the
-// match flag: a pod without a feasible match takes its first feasible node, which depends on the pod
-// only through its tolerates bit, so the wave computes the two answers on the scalar unit as
-// pair_kernel does (fn / ft during the scan, group_first_feasible_s after it) and a lane selects one.
+// match flag, plus, KX, one OR of the feasible non-matches (dm' & ~xi): 5.5 VALU per word in
+// the identity-like modes, 6.5 with KX. With KX the flag is per step (two groups) and a compare and a
+// select after each step remember the lowest step with a match (fm). The identity-like modes keep ONE
+// flag per lane and block for the whole scan above group 0 and no fm: group 0 nearly always holds
+// the lane's first match, and a lane for which it does not, while the flag says one lies above, walks
+// the groups upward from 1 (exec-masked, behind a wave-uniform branch that real tables do not take).
+// They need no other per-lane reduction: a pod without a feasible match takes its first feasible
+// node, which depends on the pod only through its tolerates bit, so the wave computes the two answers
+// on the scalar unit as pair_kernel does (fn / ft during the scan, group_first_feasible_s after it)
+// and a lane selects one. Group 0's first match comes from dm' alone there (group_firsts_lds).
 // The forms that lost their A/B (profiles/r4_ab_pair_planes.txt) are no longer built:
 // one, three and four blocks per wave; the pure-LDS full-group form (a full group always takes hybrid
 // planes: X and D3 by scalar loads, D0-D2 from LDS); compaction in the identity-like modes and hybrid
@@ -520,12 +525,51 @@ __device__ __forceinline__ uint32_t group_first_lds(const uint4* __restrict__ s_
 // when some lane needs it): the first feasible match (rm) and, KX, the first feasible non-match (rx;
 // without KX it is left alone: the caller takes the first feasible node from the scalar unit); NOFIT
 // where the group has none. Called by whole waves.
+// Without KX the first match comes out of the scan's own dm' chain and V is not read (5 planes, not
+// 6): a padding slot carries node code 15 in D0-D3 and X = 0 (msh_prep.hip node_prep_kernel and
+// table_copy_kernel write them), code 15 differs from every pod code, so dm' is zero exactly at the
+// feasible matches whether or not the group holds padding. The chain's last v_bitop3 emits the
+// complement (truth table 0x09 = ~(t | (D3 ^ P3))): a set bit marks a feasible match. Then v_ffbl per
+// word, the word's offset ORed in, and two words meet in one v_min3_u32: 7.25 VALU per word against
+// 10.75 for the form that builds the feasibility word from X, V and nT beside dm.
 template <bool KX>
 __device__ __forceinline__ void group_firsts_lds(const uint4* __restrict__ s_tab, uint32_t g, uint32_t P0,
                                                  uint32_t P1, uint32_t P2, uint32_t P3, uint32_t nT, bool digit,
                                                  uint32_t& rm, uint32_t& rx) {
   const uint4* q = s_tab + g * (GROUP_DWORDS / 4);
   uint32_t bm = 0xFFFFFFFFu, bx = 0xFFFFFFFFu;
+  if constexpr (!KX) {
+    constexpr int PLX = 4;  // pl[0..3]: D0-D3, pl[PLX]: X
+    static_assert(PLANE_X == PLX, "X follows the four code planes");
+    // the first match of one half (bit index in the group, all-ones if none); the halves are two
+    // copies of the code, so every word offset is an immediate and word 0 needs none
+    auto half = [&](auto hc) -> uint32_t {
+      constexpr int hh = decltype(hc)::value;
+      uint32_t pl[PLX + 1][4];
+#pragma unroll
+      for (int k = 0; k <= PLX; ++k) {
+        const uint4 v = q[2 * k + hh];
+        pl[k][0] = v.x; pl[k][1] = v.y; pl[k][2] = v.z; pl[k][3] = v.w;
+      }
+      uint32_t t[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        uint32_t u = __builtin_amdgcn_bitop3_b32(pl[PLX][c], nT, nT, 0xc0);  // X & nT
+        u = bop3_or_xor(u, pl[0][c], P0);
+        u = bop3_or_xor(u, pl[1][c], P1);
+        u = bop3_or_xor(u, pl[2][c], P2);
+        u = __builtin_amdgcn_bitop3_b32(u, pl[3][c], P3, 0x09);  // ~dm'
+        t[c] = lowbit(u);  // all-ones when the word has none, and stays so under the offset
+        if (c + 4 * hh != 0) t[c] |= (uint32_t)(32 * (c + 4 * hh));
+      }
+      return umin(umin(t[0], t[1]), umin(t[2], t[3]));  // v_min_u32, v_min3_u32
+    };
+    bm = half(std::integral_constant<int, 0>{});
+    // the upper half only when some lane with a digit has no match in the lower one (as below)
+    if (__ballot(digit && bm == 0xFFFFFFFFu) != 0) bm = umin(bm, half(std::integral_constant<int, 1>{}));
+    rm = bm < GROUP_NODES ? g * GROUP_NODES + bm : NOFIT;
+    return;
+  }
 #pragma unroll 1
   for (int hh = 0; hh < 2; ++hh) {
     uint32_t pl[PLANE_N][4];
@@ -559,8 +603,9 @@ __device__ __forceinline__ void group_firsts_lds(const uint4* __restrict__ s_tab
 // scan — group g-1's LDS and scalar planes requested by one asm block before group g's v_bitop3 chains,
 // one explicit wait per group — ran 81.4 against 76.7 us per 32-batch C3 launch in the identity-like
 // modes, 80.3 against 80.0 in MINMAX; the identity-like 4-wave form compiled for 8 waves per SIMD
-// (amdgpu_waves_per_eu(8): 64 VGPRs, 36 B of spills outside the scan loop, against 78 VGPRs and 6 waves)
-// ran 78.1 against 78.0 at w=3 DEFAULT and 78.6 against 78.2 at w=1 NONE.)
+// (amdgpu_waves_per_eu(8): 64 VGPRs, 36 B of spills outside the scan loop, against the 78 VGPRs and 6 waves
+// it had then) ran 78.1 against 78.0 at w=3 DEFAULT and 78.6 against 78.2 at w=1 NONE. Today's identity-like
+// instances take 56 VGPRs, 8 waves per SIMD, without the attribute: profiles/pair_one_flag_regs.json.)
 template <bool SHARD, bool KX, int W>
 __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
   constexpr bool CMP = KX && W == PL_WAVES;
@@ -653,8 +698,8 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
   }
   if (!any_act) return;  // wave-uniform; no barrier below
   // Groups above 0, descending, two per step (as pair_kernel): each group's 40 / 48 plane words read
-  // into VGPRs at once and applied to every block. fm / fx: the lower group of the lowest pair with a
-  // feasible match / KX: feasible non-match. (Reading half a group at a time, one group per iteration,
+  // into VGPRs at once and applied to every block. KX: fm / fx, the lower group of the lowest pair with a
+  // feasible match / feasible non-match. (Reading half a group at a time, one group per iteration,
   // cut the kernel to 52 VGPRs and 8 waves per SIMD but ran slower: 95.6 against 89.8 us per 32-batch
   // C3 launch, profiles/r4_ab_pair_planes.txt.)
   // Identity-like modes: fn / ft, the lowest group above 0 with a node feasible for a pod that does
@@ -663,9 +708,19 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
   // all-ones, and always one for a tolerating pod; a group with padding takes group_feasible_s<true>
   // on its X and V planes. The scan has one body: a padded group takes hybrid planes too (its match
   // flag reads no V, see pair_group_hy).
-  uint32_t fm[PL_BPW], fx[PL_BPW];
+  // Identity-like modes: one match flag per block for the whole scan (amw: the AND of every dm' word
+  // above group 0, not all-ones iff some group above 0 holds a feasible match for the lane), no fm.
+  // Which group is asked only by a lane with no match in group 0, which real tables do not produce
+  // (~1e-12 with 10 % of 256 nodes per digit), and answered then by walking the groups upward.
+  // One accumulator per block, not an even and an odd one: the per-step flag was the same serial chain
+  // of AND3s (four per group and block, each behind two five-deep dm' chains of its own), two blocks
+  // interleave, and the counters show no more waiting than before (profiles/pair_one_flag_c3.json).
+  uint32_t fm[PL_BPW], fx[PL_BPW], amw[PL_BPW];
 #pragma unroll
-  for (int b = 0; b < PL_BPW; ++b) fm[b] = fx[b] = NO_GROUP;
+  for (int b = 0; b < PL_BPW; ++b) {
+    fm[b] = fx[b] = NO_GROUP;
+    amw[b] = 0xFFFFFFFFu;
+  }
   uint32_t fn = NO_GROUP, ft = NO_GROUP;
   // KX, group 0 first: every block's first hits in it (half-group reads; the upper half only when
   // some lane needs it). When every lane already has its first feasible non-match there, the scan of
@@ -682,10 +737,11 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
     constexpr bool NOAX = decltype(noax)::value;
     constexpr bool KXS = KX && !NOAX;  // the non-match flags are tracked
     for (int32_t g = n_groups - 1; g > 0; g -= 2) {
-      uint32_t am[PL_BPW], ax[PL_BPW];
+      uint32_t ams[PL_BPW], ax[PL_BPW];
+      uint32_t(&am)[PL_BPW] = *(KX ? &ams : &amw);  // KX: the step's own flag
 #pragma unroll
       for (int b = 0; b < PL_BPW; ++b) {
-        am[b] = 0xFFFFFFFFu;
+        if constexpr (KX) am[b] = 0xFFFFFFFFu;
         ax[b] = 0u;
       }
       const int32_t g2 = g - 1 > 0 ? g - 1 : g;
@@ -743,10 +799,12 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
           }
         }
       }
+      if constexpr (KX) {
 #pragma unroll
-      for (int b = 0; b < PL_BPW; ++b) {
-        fm[b] = am[b] != 0xFFFFFFFFu ? (uint32_t)g2 : fm[b];
-        if constexpr (KXS) fx[b] = ax[b] != 0u ? (uint32_t)g2 : fx[b];
+        for (int b = 0; b < PL_BPW; ++b) {
+          fm[b] = am[b] != 0xFFFFFFFFu ? (uint32_t)g2 : fm[b];
+          if constexpr (KXS) fx[b] = ax[b] != 0u ? (uint32_t)g2 : fx[b];
+        }
       }
     }
   };
@@ -785,7 +843,18 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
   for (int b = 0; b < PL_BPW; ++b) {
     const int32_t j = jj[b];
     if (__ballot(j < np) == 0) continue;  // wave-uniform: a block of padding lanes only
-    if (rm[b] == NOFIT && fm[b] != NO_GROUP) {  // the lowest hit pair: its lower group, else the one above
+    if constexpr (!KX) {
+      // a lane without a match in group 0 whose flag says one lies above (a pod without a digit
+      // never: its code matches no node's, so its flag stays all-ones): groups 1, 2, ... until every
+      // such lane of the wave has its first. The flag guarantees a hit; n_groups bounds the walk anyway.
+      bool pend = rm[b] == NOFIT && amw[b] != 0xFFFFFFFFu;
+      for (int32_t g = 1; g < n_groups && __ballot(pend) != 0; ++g) {
+        if (pend) {
+          rm[b] = group_first_lds<0>(s_tab, (uint32_t)g, P0[b], P1[b], P2[b], P3[b], nT[b]);
+          pend = rm[b] == NOFIT;
+        }
+      }
+    } else if (rm[b] == NOFIT && fm[b] != NO_GROUP) {  // the lowest hit pair: its lower group, else the one above
       rm[b] = group_first_lds<0>(s_tab, fm[b], P0[b], P1[b], P2[b], P3[b], nT[b]);
       if (rm[b] == NOFIT) rm[b] = group_first_lds<0>(s_tab, fm[b] + 1, P0[b], P1[b], P2[b], P3[b], nT[b]);
     }
@@ -865,7 +934,8 @@ hipError_t launch_pair_t(PairArgs& a, const DeviceInfo& dev, hipStream_t s) {
   }
   if (maxp == 0) return hipSuccess;
   // LDS-staged planes when the table fits and the launch fills the chip with whole workgroups (the
-  // copy is amortised over PL_WAVES x PL_BPW blocks); scalar-loaded planes (with slice waves) otherwise
+  // copy is amortised over PL_WAVES x PL_BPW blocks); pair_kernel (with slice waves; launch_pair_s stages
+  // its planes in LDS too when the table fits, else it loads them on the scalar unit) otherwise
   // (auto: every normalize mode; per 32-batch C3 launch NONE 96.5 -> 85.0 us and MINMAX 95.4 -> 91.5 us
   // against scalar-loaded planes, profiles/r4_ab_pair_planes.txt)
   const bool fits = a.n_groups <= PAIR_LDS_MAX_GROUPS;
