@@ -982,6 +982,101 @@ func (x *Ctx) ScheduleSequentialPrefsDevice(p int, dPodDigit, dPodTol, dGroup, d
 	return nil
 }
 
+// Spread group modes (msh_set_spread_group_modes).
+const (
+	SpreadDoNotSchedule  uint8 = C.MSH_SPREAD_DO_NOT_SCHEDULE
+	SpreadScheduleAnyway uint8 = C.MSH_SPREAD_SCHEDULE_ANYWAY
+)
+
+// SetSpreadGroupModes gives each spread group its mode; len(modes) must be the current group count.
+func (x *Ctx) SetSpreadGroupModes(modes []uint8) error {
+	cm := make([]C.uint8_t, len(modes))
+	for i, m := range modes {
+		cm[i] = C.uint8_t(m)
+	}
+	if rc := C.msh_set_spread_group_modes(x.c, C.int32_t(len(modes)), ptrU8(cm)); rc != C.MSH_OK {
+		return x.lastErr("msh_set_spread_group_modes", rc)
+	}
+	return nil
+}
+
+// SpreadGroupModes returns the groups' modes, one per group.
+func (x *Ctx) SpreadGroupModes() ([]uint8, error) {
+	var g C.int32_t
+	if rc := C.msh_get_spread_group_modes(x.c, &g, nil); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_get_spread_group_modes", rc)
+	}
+	cm := make([]C.uint8_t, int(g))
+	if rc := C.msh_get_spread_group_modes(x.c, &g, ptrU8(cm)); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_get_spread_group_modes", rc)
+	}
+	modes := make([]uint8, len(cm))
+	for i, m := range cm {
+		modes[i] = uint8(m)
+	}
+	return modes, nil
+}
+
+// SetSpreadScoreWeight sets the soft spread score's plugin weight, in [0, 100]; 0 is the default.
+func (x *Ctx) SetSpreadScoreWeight(w int) error {
+	if rc := C.msh_set_spread_score_weight(x.c, C.int32_t(w)); rc != C.MSH_OK {
+		return x.lastErr("msh_set_spread_score_weight", rc)
+	}
+	return nil
+}
+
+// SpreadScoreWeight returns the soft spread score's plugin weight.
+func (x *Ctx) SpreadScoreWeight() (int, error) {
+	var w C.int32_t
+	if rc := C.msh_spread_score_weight(x.c, &w); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_spread_score_weight", rc)
+	}
+	return int(w), nil
+}
+
+// SeqSoftMaxNodes returns the largest table ScheduleSequentialSoft takes with nres resources.
+func (x *Ctx) SeqSoftMaxNodes(nres int) (int, error) {
+	var out C.int32_t
+	if rc := C.msh_seq_soft_max_nodes(x.c, C.int32_t(nres), &out); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_seq_soft_max_nodes", rc)
+	}
+	return int(out), nil
+}
+
+// ScheduleSequentialSoft is ScheduleSequentialPrefs, except that a pod of a SpreadScheduleAnyway group passes no
+// spread filter and gets the spread score instead; with no such group it is ScheduleSequentialPrefs.
+func (x *Ctx) ScheduleSequentialSoft(pods []*v1.Pod, b *HostBatch, group, class []int32, nres int, req []int64,
+	maxPodsPerNode int32) ([]Result, error) {
+	if !x.hasNodes {
+		return nil, errors.New("gpusched: UploadNodes has not been called")
+	}
+	p := len(pods)
+	if len(req) != nres*p || (group != nil && len(group) != p) || (class != nil && len(class) != p) {
+		return nil, errors.New("gpusched: req holds nres*len(pods) values, group and class len(pods)")
+	}
+	if err := x.pack(b, pods); err != nil {
+		return nil, err
+	}
+	if rc := C.msh_schedule_sequential_soft(x.c, C.int32_t(p), ptrI8(b.pd[:p]), ptrU8(b.pt[:p]), ptrI32(toI32(group)),
+		ptrI32(toI32(class)), C.int32_t(nres), ptrI64(toI64(req)), C.int32_t(maxPodsPerNode), ptrI32(b.idx[:p]),
+		ptrI64(b.score[:p]), ptrI32(b.status[:p]), nil, nil); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_schedule_sequential_soft", rc)
+	}
+	return x.results(b), nil
+}
+
+// ScheduleSequentialSoftDevice is the asynchronous form over device pointers (msh_schedule_sequential_soft_device);
+// as ScheduleSequentialPrefsDevice.
+func (x *Ctx) ScheduleSequentialSoftDevice(p int, dPodDigit, dPodTol, dGroup, dClass unsafe.Pointer, nres int,
+	dReq unsafe.Pointer, maxPodsPerNode int32, dIdx, dScore, dStatus, stream unsafe.Pointer) error {
+	if rc := C.msh_schedule_sequential_soft_device(x.c, C.int32_t(p), (*C.int8_t)(dPodDigit), (*C.uint8_t)(dPodTol),
+		(*C.int32_t)(dGroup), (*C.int32_t)(dClass), C.int32_t(nres), (*C.int64_t)(dReq), C.int32_t(maxPodsPerNode),
+		(*C.int32_t)(dIdx), (*C.int64_t)(dScore), (*C.int32_t)(dStatus), stream); rc != C.MSH_OK {
+		return x.lastErr("msh_schedule_sequential_soft_device", rc)
+	}
+	return nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

@@ -665,6 +665,58 @@ int msh_schedule_sequential_prefs_device(msh_ctx* ctx, int32_t p, const int8_t* 
                                          const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
                                          int64_t* d_out_score, int32_t* d_out_status, void* stream);
 
+/* Soft topology spread: PodTopologySpread's scoring half, whenUnsatisfiable: ScheduleAnyway (upstream v1.22,
+ * podtopologyspread/scoring.go, one constraint per group and the zone key; additive in ABI 8).
+ * Group modes. msh_set_spread_group_modes gives each of the ctx's G spread groups a mode, MSH_SPREAD_DO_NOT_SCHEDULE
+ *   (the default of every group: the hard filter) or MSH_SPREAD_SCHEDULE_ANYWAY. G different from the current group
+ *   count, or a value above 1: MSH_ERR_INVALID. msh_get_spread_group_modes reads *out_G and the G modes back (either
+ *   may be NULL). msh_set_spread_groups with a different G resets every mode to the default, with the same G it keeps
+ *   them. Counts, zones and skews keep their lifetime rules.
+ * msh_set_spread_score_weight: the plugin weight w_spread in [0, 100] (else MSH_ERR_INVALID), default 0.
+ * msh_schedule_sequential_soft / _soft_device take msh_schedule_sequential_prefs' arguments and contract. A pod whose
+ *   group g is SCHEDULE_ANYWAY passes through no spread filter: its feasible set F is the one of an ungrouped pod of
+ *   its class, nodes with zone < 0 included. With Zs the zones of the zoned nodes in F and size = |Zs|:
+ *     raw_z = Round(double(cnt[g][z]) * log(size + 2) + double(max_skew[g] - 1)) for z in Zs, the product and the sum
+ *       two separately rounded IEEE double operations (no fused multiply-add), Round half away from zero, the 65
+ *       values log(size + 2) computed once by the library's std::log (msh_spread_soft_weight returns them; size
+ *       outside [0, MSH_MAX_ZONES] or a NULL output: MSH_ERR_INVALID);
+ *     mx = max raw_z, mn = min raw_z over Zs;
+ *     ns_i = 100 if mx == 0 else 100 * (mx + mn - raw_zone[i]) / mx, truncated, for i in F with zone[i] >= 0;
+ *     ns_i = 0 for i in F with zone[i] < 0, and on every node when Zs is empty;
+ *     total_i = _prefs' total_i + w_spread * ns_i,
+ *   the first maximum in List order wins and out_score is that total. An ungrouped pod and a pod of a
+ *   DO_NOT_SCHEDULE group have ns = 0 everywhere and are decided exactly as _prefs decides them. The commit is
+ *   _prefs'; a placed pod of a soft group adds 1 to cnt[g][zone[sel]] only when zone[sel] >= 0.
+ *   With no SCHEDULE_ANYWAY group on the ctx the call is _prefs itself, bit for bit, the same kernel instance,
+ *   whatever w_spread is. With one, the checks are those of a _prefs call with a nonzero preference weight (the class
+ *   masks are not required by themselves) whatever the preference weights are.
+ * Refusals are _prefs', in its order, then: 100 * (W_res + w_affinity + w_taint + w_spread) > 65,534:
+ *   MSH_ERR_UNSUPPORTED; and, for a call with pod groups, MSH_ERR_UNSUPPORTED when a spread count may exceed
+ *   MSH_SPREAD_SOFT_MAX (the library keeps an upper bound: the largest count at the last msh_patch_spread_counts,
+ *   0 when the counts were zeroed, plus the pods submitted to calls with groups since), when p exceeds it, or when
+ *   a SCHEDULE_ANYWAY group's max_skew does.
+ * Node limits: msh_seq_soft_max_nodes, _prefs' limits.
+ * The other calls that take pod_group (_spread, _spread_scored, _classes, _prefs) refuse with MSH_ERR_UNSUPPORTED and
+ *   a message naming msh_schedule_sequential_soft when the ctx holds a SCHEDULE_ANYWAY group and pod_group is
+ *   non-NULL; with every mode at its default nothing about them changes. A failed call changes nothing. */
+#define MSH_SPREAD_DO_NOT_SCHEDULE 0
+#define MSH_SPREAD_SCHEDULE_ANYWAY 1
+#define MSH_SPREAD_SOFT_MAX (1 << 24)
+int msh_set_spread_group_modes(msh_ctx* ctx, int32_t G, const uint8_t* mode);
+int msh_get_spread_group_modes(const msh_ctx* ctx, int32_t* out_G, uint8_t* out_mode);
+int msh_set_spread_score_weight(msh_ctx* ctx, int32_t w_spread);
+int msh_spread_score_weight(const msh_ctx* ctx, int32_t* out_w_spread);
+int msh_spread_soft_weight(int32_t size, double* out);
+int msh_seq_soft_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t* out_max_nodes);
+int msh_schedule_sequential_soft(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                 const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                 const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                 int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_soft_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                        const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
+                                        const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
+                                        int64_t* d_out_score, int32_t* d_out_status, void* stream);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

@@ -59,6 +59,8 @@ RESOURCE_SCORE_MAX = 1 << 55            # MSH_RESOURCE_SCORE_MAX: the largest am
 
 MAX_ZONES = 64           # MSH_MAX_ZONES: zone ids are in [0, MAX_ZONES), -1 = the node has no zone
 MAX_SPREAD_GROUPS = 128  # MSH_MAX_SPREAD_GROUPS
+SPREAD_DO_NOT_SCHEDULE, SPREAD_SCHEDULE_ANYWAY = 0, 1  # MSH_SPREAD_*: a spread group's mode
+SPREAD_SOFT_MAX = 1 << 24  # MSH_SPREAD_SOFT_MAX: counts, pods per call and skews of a SCHEDULE_ANYWAY group
 MAX_POD_CLASSES = 64     # MSH_MAX_POD_CLASSES: pod classes are in [0, C), C <= MAX_POD_CLASSES, -1 = no class
 
 MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
@@ -87,6 +89,9 @@ EXPORTED = (
     "msh_upload_node_class_prefs", "msh_patch_node_class_prefs", "msh_clear_node_class_prefs", "msh_node_class_prefs",
     "msh_set_preference_weights", "msh_preference_weights", "msh_seq_prefs_max_nodes",
     "msh_schedule_sequential_prefs", "msh_schedule_sequential_prefs_device",
+    "msh_set_spread_group_modes", "msh_get_spread_group_modes", "msh_set_spread_score_weight", "msh_spread_score_weight",
+    "msh_spread_soft_weight", "msh_seq_soft_max_nodes", "msh_schedule_sequential_soft",
+    "msh_schedule_sequential_soft_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -234,6 +239,14 @@ _SIGS = {
     "msh_seq_prefs_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_schedule_sequential_prefs": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
     "msh_schedule_sequential_prefs_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "msh_set_spread_group_modes": (C.c_int, [_P, _I32, _P]),
+    "msh_get_spread_group_modes": (C.c_int, [_P, C.POINTER(_I32), _P]),
+    "msh_set_spread_score_weight": (C.c_int, [_P, _I32]),
+    "msh_spread_score_weight": (C.c_int, [_P, C.POINTER(_I32)]),
+    "msh_spread_soft_weight": (C.c_int, [_I32, C.POINTER(C.c_double)]),
+    "msh_seq_soft_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
+    "msh_schedule_sequential_soft": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_soft_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

@@ -222,6 +222,28 @@ def preference_key(pod: Any) -> str:
     return json.dumps([_plain(pod_preferred_terms(pod)), tols], sort_keys=True)
 
 
+SPREAD_MODES = {"DoNotSchedule": 0, "ScheduleAnyway": 1}  # MSH_SPREAD_DO_NOT_SCHEDULE / MSH_SPREAD_SCHEDULE_ANYWAY
+
+
+def spread_mode(pod: Any, topology_key: str) -> int | None:
+    """The mode of the pod's topology spread constraint on `topology_key` as DeviceContext.set_spread_group_modes
+    takes it: spec.topologySpreadConstraints[*].whenUnsatisfiable of the first constraint with that key, DoNotSchedule
+    (the API's default, also for an absent field) -> 0, ScheduleAnyway -> 1. None when the pod has no constraint on
+    the key; any other value raises ValueError (the API server rejects it)."""
+    if hasattr(pod, "topology_spread_constraints"):
+        cons = pod.topology_spread_constraints
+    else:
+        cons = _get(pod, "spec", "topologySpreadConstraints")
+    for con in cons or ():
+        if _get(con, "topologyKey") != topology_key:
+            continue
+        when = _get(con, "whenUnsatisfiable") or "DoNotSchedule"
+        if when not in SPREAD_MODES:
+            raise ValueError(f"whenUnsatisfiable is DoNotSchedule or ScheduleAnyway, not {when!r}")
+        return SPREAD_MODES[when]
+    return None
+
+
 def _plain(x: Any) -> Any:
     """A JSON-able copy of the public fields of x (dicts, sequences, attribute objects)."""
     if isinstance(x, Mapping):

@@ -17,7 +17,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdint>
@@ -404,6 +406,7 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
     c->counts_dirty = false;
     if (c->d_spread_cnt)  // the spread counts belonged to the previous table's nodes
       MSH_HIP(c, hipMemsetAsync(c->d_spread_cnt, 0, (size_t)MSH_MAX_SPREAD_GROUPS * MSH_MAX_ZONES * sizeof(int32_t), ps));
+    c->sp_cnt_bound = 0;
   }
   MSH_HIP(c, hipStreamSynchronize(ps));
   if (up) {  // the capacity column belonged to the previous table's nodes
@@ -814,6 +817,7 @@ void msh_destroy(msh_ctx* c) {
   (void)hipFree(c->d_pref);
   (void)hipFree(c->d_skew);
   (void)hipFree(c->d_spread_cnt);
+  (void)hipFree(c->d_zone_weight);
   for (hipEvent_t e : c->async_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->tev) {
@@ -1709,7 +1713,23 @@ int spread_alloc(msh_ctx* c) {
 
 int spread_zero_counts(msh_ctx* c) {
   MSH_HIP(c, hipMemsetAsync(c->d_spread_cnt, 0, SPREAD_CNT_BYTES, c->prep_stream));
+  c->sp_cnt_bound = 0;
   return MSH_OK;
+}
+
+// A call that takes pod groups on a ctx with a SCHEDULE_ANYWAY group is msh_schedule_sequential_soft's alone: the
+// other entry points would run the group's pods through the hard filter. An explicit error, never a fallback.
+int refuse_soft_groups(msh_ctx* c, const char* entry, bool grouped) {
+  if (!grouped || c->sp_soft == 0) return MSH_OK;
+  return fail(c, MSH_ERR_UNSUPPORTED,
+              std::string(entry) + ": the ctx holds " + std::to_string(c->sp_soft) +
+                  " SCHEDULE_ANYWAY spread group(s) (msh_set_spread_group_modes); a call with pod groups must be "
+                  "msh_schedule_sequential_soft");
+}
+
+// p pods went to a launch with groups: each may have raised one count by one (sp_cnt_bound)
+void spread_bound_add(msh_ctx* c, bool grouped, int32_t p) {
+  if (grouped) c->sp_cnt_bound += p;
 }
 }  // namespace
 
@@ -1790,8 +1810,72 @@ int msh_set_spread_groups(msh_ctx* c, int32_t G, const int32_t* max_skew) {
   }
   if (G != c->sp_groups && (rc = spread_zero_counts(c)) != MSH_OK) return rc;  // the rows mean other groups now
   MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  if (G != c->sp_groups) {  // other groups: every mode back to the default
+    c->h_spmode.assign((size_t)G, (uint8_t)MSH_SPREAD_DO_NOT_SCHEDULE);
+    c->sp_soft = 0;
+  }
   c->sp_groups = G;
   c->h_skew.assign(max_skew, max_skew + G);
+  return MSH_OK;
+}
+
+int msh_set_spread_group_modes(msh_ctx* c, int32_t G, const uint8_t* mode) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (G != c->sp_groups)
+    return fail(c, MSH_ERR_INVALID, "modes for " + std::to_string(G) + " groups, msh_set_spread_groups set " +
+                                        std::to_string(c->sp_groups));
+  if (G > 0 && !mode) return fail(c, MSH_ERR_INVALID, "null mode array");
+  int32_t soft = 0;
+  for (int32_t k = 0; k < G; ++k) {
+    if (mode[k] > MSH_SPREAD_SCHEDULE_ANYWAY)
+      return fail(c, MSH_ERR_INVALID, "mode above MSH_SPREAD_SCHEDULE_ANYWAY at group " + std::to_string(k));
+    soft += mode[k] == MSH_SPREAD_SCHEDULE_ANYWAY ? 1 : 0;
+  }
+  c->h_spmode.assign(mode, mode + G);  // host only: a launch takes the modes as kernel arguments
+  c->sp_soft = soft;
+  return MSH_OK;
+}
+
+int msh_get_spread_group_modes(const msh_ctx* c, int32_t* out_G, uint8_t* out_mode) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_G) *out_G = c->sp_groups;
+  if (out_mode)
+    for (int32_t k = 0; k < c->sp_groups; ++k)
+      out_mode[k] = (size_t)k < c->h_spmode.size() ? c->h_spmode[(size_t)k] : (uint8_t)MSH_SPREAD_DO_NOT_SCHEDULE;
+  return MSH_OK;
+}
+
+int msh_set_spread_score_weight(msh_ctx* c, int32_t w_spread) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (w_spread < 0 || w_spread > 100) return fail(c, MSH_ERR_INVALID, "spread score weight outside [0, 100]");
+  c->w_spread = w_spread;
+  return MSH_OK;
+}
+
+int msh_spread_score_weight(const msh_ctx* c, int32_t* out_w_spread) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_w_spread) *out_w_spread = c->w_spread;
+  return MSH_OK;
+}
+
+namespace {
+// upstream's topologyNormalizingWeight for size = 0..MSH_MAX_ZONES zones, log(size + 2): this library's std::log,
+// computed once; the kernel multiplies by these values and msh_spread_soft_weight returns them
+const double* soft_weights() {
+  static const std::array<double, MSH_MAX_ZONES + 1> w = [] {
+    std::array<double, MSH_MAX_ZONES + 1> t{};
+    for (int32_t k = 0; k <= MSH_MAX_ZONES; ++k) t[(size_t)k] = std::log((double)(k + 2));
+    return t;
+  }();
+  return w.data();
+}
+}  // namespace
+
+int msh_spread_soft_weight(int32_t size, double* out) {
+  if (!out || size < 0 || size > MSH_MAX_ZONES) return MSH_ERR_INVALID;
+  *out = soft_weights()[size];
   return MSH_OK;
 }
 
@@ -1846,6 +1930,8 @@ int msh_patch_spread_counts(msh_ctx* c, int32_t count, const int32_t* gi, const 
   for (int32_t k = 0; k < count; ++k) st[keys[(size_t)k]] = value[k];
   MSH_HIP(c, hipMemcpyAsync(c->d_spread_cnt, st, SPREAD_CNT_BYTES, hipMemcpyHostToDevice, c->prep_stream));
   MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  // the whole table is at hand: its largest count, exactly
+  c->sp_cnt_bound = *std::max_element(st, st + (size_t)c->sp_groups * MSH_MAX_ZONES);
   return MSH_OK;
 }
 
@@ -1899,8 +1985,9 @@ int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t
                  bool scored_entry) {
   if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
-  int rc = refuse_random(c, entry);
+  int rc = refuse_soft_groups(c, entry, true);  // a spread call always has groups
   if (rc != MSH_OK) return rc;
+  if ((rc = refuse_random(c, entry)) != MSH_OK) return rc;
   if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   if (scored && !scored_entry)
@@ -2007,6 +2094,7 @@ int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_
     return hip_fail(c, e, scored ? "seq_spread_score_kernel" : "seq_spread_kernel");
   }
   c->counts_dirty = false;  // the one workgroup folded the replicas
+  spread_bound_add(c, d_pod_group != nullptr, p);
   return track_launch(c, s, true);
 }
 }  // namespace
@@ -2219,8 +2307,9 @@ int classes_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_
                   bool classed) {
   if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
-  int rc = refuse_random(c, entry);
+  int rc = refuse_soft_groups(c, entry, grouped);
   if (rc != MSH_OK) return rc;
+  if ((rc = refuse_random(c, entry)) != MSH_OK) return rc;
   if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
@@ -2289,6 +2378,7 @@ int classes_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod
     return hip_fail(c, e, scored ? "seq_classes_score_kernel" : "seq_classes_kernel");
   }
   c->counts_dirty = false;  // the one workgroup folded the replicas
+  spread_bound_add(c, d_pod_group != nullptr, p);
   return track_launch(c, s, true);
 }
 }  // namespace
@@ -2513,11 +2603,12 @@ int32_t prefs_classes(const msh_ctx* c) { return c->have_prefs ? c->pref_classes
 // (the class column is not required by itself), with the preference kernel's table limits, then the two of this
 // call: pod classes with neither column (and columns of unequal C), and a weighted sum the packed key cannot hold.
 int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node, bool grouped,
-                bool classed) {
+                bool classed, bool soft_entry = false) {
   if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
-  int rc = refuse_random(c, entry);
+  int rc = soft_entry ? MSH_OK : refuse_soft_groups(c, entry, grouped);
   if (rc != MSH_OK) return rc;
+  if ((rc = refuse_random(c, entry)) != MSH_OK) return rc;
   if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
@@ -2534,8 +2625,9 @@ int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t 
       return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
                                         " resources, the call has " + std::to_string(nres));
   }
-  const int32_t lim = msh::seq_prefs_max_nodes(nres);
-  if (c->n_nodes > lim) return fail(c, MSH_ERR_UNSUPPORTED, msh::seq_table_limit_message("preference", lim, nres));
+  const int32_t lim = soft_entry ? msh::seq_soft_max_nodes(nres) : msh::seq_prefs_max_nodes(nres);
+  if (c->n_nodes > lim)
+    return fail(c, MSH_ERR_UNSUPPORTED, msh::seq_table_limit_message(soft_entry ? "soft-spread" : "preference", lim, nres));
   if (scored && c->res_max > MSH_RESOURCE_SCORE_MAX)
     return fail(c, MSH_ERR_UNSUPPORTED,
                 "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
@@ -2549,25 +2641,62 @@ int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t 
   if (100 * wsum > 65534)
     return fail(c, MSH_ERR_UNSUPPORTED, "the weights of the resource score and the two preference scores sum to " +
                                             std::to_string(wsum) + ": the packed key holds 100 x 655 at most");
+  if (!soft_entry) return MSH_OK;
+  // msh_schedule_sequential_soft's own two, after the others: the key with the spread weight, and the counts' bound
+  if (100 * (wsum + c->w_spread) > 65534)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "the weights of the resource score, the two preference scores and the spread score sum to " +
+                    std::to_string(wsum + c->w_spread) + ": the packed key holds 100 x 655 at most");
+  if (grouped) {
+    if (c->sp_cnt_bound > MSH_SPREAD_SOFT_MAX)
+      return fail(c, MSH_ERR_UNSUPPORTED, "a spread count may have reached " + std::to_string(c->sp_cnt_bound) +
+                                              ", above MSH_SPREAD_SOFT_MAX = 2^24 (msh_reset_spread_counts zeroes them)");
+    if (p > MSH_SPREAD_SOFT_MAX)
+      return fail(c, MSH_ERR_UNSUPPORTED, "a soft-spread call takes at most MSH_SPREAD_SOFT_MAX = 2^24 pods");
+    for (int32_t g = 0; g < c->sp_groups; ++g)
+      if (c->h_spmode[(size_t)g] == MSH_SPREAD_SCHEDULE_ANYWAY && c->h_skew[(size_t)g] > MSH_SPREAD_SOFT_MAX)
+        return fail(c, MSH_ERR_UNSUPPORTED, "SCHEDULE_ANYWAY group " + std::to_string(g) + " has max_skew " +
+                                                std::to_string(c->h_skew[(size_t)g]) +
+                                                ", above MSH_SPREAD_SOFT_MAX = 2^24");
+  }
   return MSH_OK;
 }
 
+// the weights log(size + 2) on the device, uploaded once (synchronous)
+int soft_weights_device(msh_ctx* c) {
+  if (c->d_zone_weight) return MSH_OK;
+  double* d = nullptr;
+  const size_t bytes = (size_t)(MSH_MAX_ZONES + 1) * sizeof(double);
+  MSH_HIP(c, hipMalloc(&d, bytes));
+  const hipError_t e = hipMemcpy(d, soft_weights(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return hip_fail(c, e, "spread score weights");
+  }
+  c->d_zone_weight = d;
+  return MSH_OK;
+}
+
+// soft: msh_schedule_sequential_soft on a ctx with a SCHEDULE_ANYWAY group (seq_soft_kernel); else the preference call
 int prefs_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
                  const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
                  int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
-                 void* stream) {
+                 void* stream, bool soft = false) {
   c->err.clear();
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // group, class and score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
   if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr);
+  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr, soft);
   if (rc != MSH_OK) return rc;
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  if (d_pod_class && (rc = prefs_table(c, msh::seq_prefs_npl(nres))) != MSH_OK) return rc;
-  msh::PrefArgs pa{};
+  static_assert(msh::SPREAD_SOFT_MAX == MSH_SPREAD_SOFT_MAX, "the kernel's bound is the header's");
+  if (d_pod_class && (rc = prefs_table(c, soft ? msh::seq_soft_npl(nres) : msh::seq_prefs_npl(nres))) != MSH_OK) return rc;
+  if (soft && (rc = soft_weights_device(c)) != MSH_OK) return rc;
+  msh::SoftArgs so{};
+  msh::PrefArgs& pa = so.p;
   pa.ss.s = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
                         d_out_score, d_out_status);
   if (scored) spread_score_setting(c, nres, pa.ss);  // else weight 0, every resource weight 0 and the magic 0: rs = 0
@@ -2585,13 +2714,22 @@ int prefs_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_d
   hipError_t e;
   {
     TimedLaunch tl(c);
-    e = msh::launch_seq_prefs(pa, s, &err);
+    if (soft) {
+      for (int32_t k = 0; d_pod_group && k < c->sp_groups; ++k)
+        if (c->h_spmode[(size_t)k] == MSH_SPREAD_SCHEDULE_ANYWAY) so.soft[k >> 6] |= uint64_t(1) << (k & 63);
+      so.w_spread = (uint32_t)c->w_spread;
+      so.zone_weight = c->d_zone_weight;
+      e = msh::launch_seq_soft(so, s, &err);
+    } else {
+      e = msh::launch_seq_prefs(pa, s, &err);
+    }
   }
   if (e != hipSuccess) {
     if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
-    return hip_fail(c, e, "seq_prefs_kernel");
+    return hip_fail(c, e, soft ? "seq_soft_kernel" : "seq_prefs_kernel");
   }
   c->counts_dirty = false;  // the one workgroup folded the replicas
+  spread_bound_add(c, d_pod_group != nullptr, p);
   return track_launch(c, s, true);
 }
 }  // namespace
@@ -2608,20 +2746,18 @@ int msh_schedule_sequential_prefs_device(msh_ctx* c, int32_t p, const int8_t* d_
                       nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
 }
 
-int msh_schedule_sequential_prefs(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                  const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
-                                  const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
-                                  int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  const char* entry = "msh_schedule_sequential_prefs";
-  if (!c) return MSH_ERR_INVALID;
-  if (c->w_aff == 0 && c->w_taint == 0)  // nothing to add: _classes itself
-    return msh_schedule_sequential_classes(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
-                                           max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+namespace {
+// msh_schedule_sequential_prefs with a nonzero preference weight, and msh_schedule_sequential_soft on a ctx with a
+// SCHEDULE_ANYWAY group (soft)
+int prefs_host(msh_ctx* c, const char* entry, bool soft, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+               const int32_t* pod_group, const int32_t* pod_class, int32_t nres, const int64_t* pod_req,
+               int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score, int32_t* out_status,
+               msh_commit_cb commit_cb, void* user) {
   c->err.clear();
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // group, class and score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
   if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
-  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr);
+  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr, soft);
   if (rc != MSH_OK) return rc;
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   const int32_t C = prefs_classes(c);
@@ -2654,13 +2790,58 @@ int msh_schedule_sequential_prefs(msh_ctx* c, int32_t p, const int8_t* pod_digit
   if (pod_class) std::memcpy(sc, pod_class, cbytes);
   rc = prefs_device(c, entry, p, io.d_pd, io.d_pt, pod_group ? sg : nullptr, pod_class ? sc : nullptr, nres,
                     reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
-                    io.o_status, c->stream);
+                    io.o_status, c->stream, soft);
   if (rc != MSH_OK) return rc;
   if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
   if (commit_cb)
     for (int32_t j = 0; j < p; j++)
       if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
   return MSH_OK;
+}
+}  // namespace
+
+int msh_schedule_sequential_prefs(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                  const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                  const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                  int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  if (!c) return MSH_ERR_INVALID;
+  if (c->w_aff == 0 && c->w_taint == 0)  // nothing to add: _classes itself
+    return msh_schedule_sequential_classes(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
+                                           max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+  return prefs_host(c, "msh_schedule_sequential_prefs", false, p, pod_digit, pod_tol, pod_group, pod_class, nres,
+                    pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+}
+
+// Soft topology spread. With no SCHEDULE_ANYWAY group on the ctx there is nothing to add to any pod: the call is
+// _prefs itself, its kernel instance, whatever the spread weight is.
+int msh_seq_soft_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = msh::seq_soft_max_nodes(nres);
+  return MSH_OK;
+}
+
+int msh_schedule_sequential_soft_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                        const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
+                                        const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
+                                        int64_t* d_out_score, int32_t* d_out_status, void* stream) {
+  if (!c) return MSH_ERR_INVALID;
+  if (c->sp_soft == 0)
+    return msh_schedule_sequential_prefs_device(c, p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class, nres, d_pod_req,
+                                                max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+  return prefs_device(c, "msh_schedule_sequential_soft_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
+                      nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, true);
+}
+
+int msh_schedule_sequential_soft(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                 const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                 const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                 int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  if (!c) return MSH_ERR_INVALID;
+  if (c->sp_soft == 0)
+    return msh_schedule_sequential_prefs(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
+                                         max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+  return prefs_host(c, "msh_schedule_sequential_soft", true, p, pod_digit, pod_tol, pod_group, pod_class, nres,
+                    pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
 }
 
 int msh_keys_slot1_is_any(const msh_ctx* c, int32_t* out_flag) {

@@ -115,6 +115,16 @@ struct msh_ctx {
   std::vector<int32_t> h_skew;
   int32_t* d_skew = nullptr;
   int32_t* d_spread_cnt = nullptr;
+  // soft topology spread (msh_schedule_sequential_soft): each group's mode (sp_groups of them, host only: a launch
+  // takes the soft groups as two words of kernel argument), how many are SCHEDULE_ANYWAY, the score's weight, and
+  // sp_cnt_bound, an upper bound of every count cnt[g][z]: the largest value a patch wrote since the counts were last
+  // zeroed plus the pods submitted to grouped calls since then. d_zone_weight: the 65 values log(size + 2) on the
+  // device, uploaded by the first soft launch.
+  std::vector<uint8_t> h_spmode;
+  int32_t sp_soft = 0;
+  int32_t w_spread = 0;
+  int64_t sp_cnt_bound = 0;
+  double* d_zone_weight = nullptr;
   // the per-class node masks (msh_upload_node_class_bits), unversioned like the capacity column: class_cap uint64
   // on the device (the padding slots 0), the host copy (n_nodes words, what msh_node_class_bits returns) and the
   // number of classes C the column was uploaded for; dropped by msh_upload_nodes. Only

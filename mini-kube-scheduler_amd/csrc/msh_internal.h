@@ -373,6 +373,22 @@ struct PrefArgs {
 int32_t seq_prefs_max_nodes(int32_t nres);
 int32_t seq_prefs_npl(int32_t nres);
 hipError_t launch_seq_prefs(const PrefArgs& a, hipStream_t s, std::string* err);
+// The soft-spread form (msh_seq_soft.hip, msh_schedule_sequential_soft on a ctx with a SCHEDULE_ANYWAY group): the
+// preference form, except that a pod of a soft group passes no spread filter and every feasible node with a zone
+// gets w_spread * ns added, ns upstream's normalised PodTopologySpread score over the zones of the pod's feasible
+// nodes. 100 * (p.ss.weight + p.w_aff + p.w_taint + w_spread) must be <= 65,534, every count of a soft group during
+// the call <= 2 * SPREAD_SOFT_MAX and every soft group's max_skew <= SPREAD_SOFT_MAX (checked on the host).
+constexpr int32_t SPREAD_SOFT_MAX = 1 << 24;  // MSH_SPREAD_SOFT_MAX
+struct SoftArgs {
+  PrefArgs p;
+  uint64_t soft[SPREAD_MAX_GROUPS / 64];  // bit g: group g is SCHEDULE_ANYWAY
+  uint32_t w_spread;                      // the weight, [0, 100]
+  const double* zone_weight;              // [SPREAD_ZONES + 1]: log(size + 2), the host's std::log (device memory)
+};
+// Nodes the soft-spread kernel holds: the preference kernel's.
+int32_t seq_soft_max_nodes(int32_t nres);
+int32_t seq_soft_npl(int32_t nres);
+hipError_t launch_seq_soft(const SoftArgs& a, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

@@ -703,6 +703,11 @@ class DeviceContext:
         """msh_schedule_sequential_prefs: schedule_sequential_classes with w_affinity * na + w_taint * nt added to
         every feasible node's total, na and nt normalised per pod over its feasible nodes. With both weights 0 it is
         schedule_sequential_classes."""
+        return self._prefs_call("schedule_sequential_prefs", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                max_pods_per_node, on_commit, out)
+
+    def _prefs_call(self, name, pod_digit, pod_tol, pod_group, pod_class, pod_req, max_pods_per_node, on_commit, out):
+        """schedule_sequential_prefs and schedule_sequential_soft: the same arguments, msh_<name>."""
         pod_digit = np.ascontiguousarray(pod_digit, np.int8)
         pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
         cols = [pod_digit, pod_tol]
@@ -712,7 +717,7 @@ class DeviceContext:
         if pod_class is not None:
             pod_class = self._int32s(pod_class, "pod_class")
             cols.append(pod_class)
-        p = _same_len("schedule_sequential_prefs", *cols)
+        p = _same_len(name, *cols)
         nres = 0
         if pod_req is not None:
             pod_req = self._amounts(pod_req)
@@ -721,7 +726,7 @@ class DeviceContext:
             nres = pod_req.shape[0]
         idx, score, status = self._outputs(p, out)
         cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
-        self._check(self._lib.msh_schedule_sequential_prefs(
+        self._check(getattr(self._lib, "msh_" + name)(
             self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), N.ptr(pod_class), nres,
             N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
         return idx, score, status
@@ -731,6 +736,57 @@ class DeviceContext:
                                          d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_prefs_device (asynchronous on `stream`; as schedule_sequential_classes_device)."""
         self._check(self._lib.msh_schedule_sequential_prefs_device(
+            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
+            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+
+    # -- soft topology spread (whenUnsatisfiable: ScheduleAnyway) --
+    def set_spread_group_modes(self, modes) -> None:
+        """msh_set_spread_group_modes: one mode per spread group, SPREAD_DO_NOT_SCHEDULE (0, the default: the hard
+        filter) or SPREAD_SCHEDULE_ANYWAY (1: no filter, the spread score). The length must be the group count."""
+        m = np.asarray(modes)
+        if m.ndim != 1 or (m.size and (m.dtype.kind not in "iub" or m.min() < 0 or m.max() > 255)):
+            raise ValueError("modes is a flat array of 0 / 1")
+        m = np.ascontiguousarray(m, np.uint8)
+        self._check(self._lib.msh_set_spread_group_modes(self.handle, len(m), N.ptr(m) if len(m) else None))
+
+    def spread_group_modes(self) -> np.ndarray:
+        """msh_get_spread_group_modes: the groups' modes (uint8, one per group)."""
+        g = C.c_int32(0)
+        self._check(self._lib.msh_get_spread_group_modes(self.handle, C.byref(g), None))
+        out = np.zeros(g.value, np.uint8)
+        self._check(self._lib.msh_get_spread_group_modes(self.handle, C.byref(g), N.ptr(out) if g.value else None))
+        return out
+
+    def set_spread_score_weight(self, weight: int = 0) -> None:
+        """msh_set_spread_score_weight: the plugin weight of the soft spread score, in [0, 100]."""
+        self._check(self._lib.msh_set_spread_score_weight(self.handle, int(weight)))
+
+    def spread_score_weight(self) -> int:
+        w = C.c_int32()
+        self._check(self._lib.msh_spread_score_weight(self.handle, C.byref(w)))
+        return w.value
+
+    def seq_soft_max_nodes(self, nres: int = 0) -> int:
+        """msh_seq_soft_max_nodes: the largest table schedule_sequential_soft takes with nres (0..4) resources."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_soft_max_nodes(self.handle, int(nres), C.byref(out)))
+        return out.value
+
+    def schedule_sequential_soft(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_group=None, pod_class=None,
+                                 pod_req=None, max_pods_per_node: int = 0,
+                                 on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_soft: schedule_sequential_prefs, except that a pod of a SCHEDULE_ANYWAY group passes
+        no spread filter and w_spread * ns is added to every feasible node with a zone, ns upstream's normalised
+        PodTopologySpread score over the zones of the pod's feasible nodes. With no such group it is
+        schedule_sequential_prefs."""
+        return self._prefs_call("schedule_sequential_soft", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                max_pods_per_node, on_commit, out)
+
+    def schedule_sequential_soft_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
+                                        d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
+                                        d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
+        """msh_schedule_sequential_soft_device (asynchronous on `stream`; as schedule_sequential_prefs_device)."""
+        self._check(self._lib.msh_schedule_sequential_soft_device(
             self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
             d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
 
