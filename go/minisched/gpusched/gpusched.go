@@ -1077,6 +1077,66 @@ func (x *Ctx) ScheduleSequentialSoftDevice(p int, dPodDigit, dPodTol, dGroup, dC
 	return nil
 }
 
+// SetBalancedScore sets NodeResourcesBalancedAllocation's plugin weight, in [0, 100]; 0 is the default.
+func (x *Ctx) SetBalancedScore(w int) error {
+	if rc := C.msh_set_balanced_score(x.c, C.int32_t(w)); rc != C.MSH_OK {
+		return x.lastErr("msh_set_balanced_score", rc)
+	}
+	return nil
+}
+
+// BalancedScore returns the balanced-allocation score's plugin weight.
+func (x *Ctx) BalancedScore() (int, error) {
+	var w C.int32_t
+	if rc := C.msh_balanced_score(x.c, &w); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_balanced_score", rc)
+	}
+	return int(w), nil
+}
+
+// SeqBalancedMaxNodes returns the largest table ScheduleSequentialBalanced takes with nres resources.
+func (x *Ctx) SeqBalancedMaxNodes(nres int) (int, error) {
+	var out C.int32_t
+	if rc := C.msh_seq_balanced_max_nodes(x.c, C.int32_t(nres), &out); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_seq_balanced_max_nodes", rc)
+	}
+	return int(out), nil
+}
+
+// ScheduleSequentialBalanced is ScheduleSequentialSoft with the balanced-allocation score of the table's first two
+// resources, times its weight, added to every feasible node's total; with the weight 0 it is ScheduleSequentialSoft.
+func (x *Ctx) ScheduleSequentialBalanced(pods []*v1.Pod, b *HostBatch, group, class []int32, nres int, req []int64,
+	maxPodsPerNode int32) ([]Result, error) {
+	if !x.hasNodes {
+		return nil, errors.New("gpusched: UploadNodes has not been called")
+	}
+	p := len(pods)
+	if len(req) != nres*p || (group != nil && len(group) != p) || (class != nil && len(class) != p) {
+		return nil, errors.New("gpusched: req holds nres*len(pods) values, group and class len(pods)")
+	}
+	if err := x.pack(b, pods); err != nil {
+		return nil, err
+	}
+	if rc := C.msh_schedule_sequential_balanced(x.c, C.int32_t(p), ptrI8(b.pd[:p]), ptrU8(b.pt[:p]), ptrI32(toI32(group)),
+		ptrI32(toI32(class)), C.int32_t(nres), ptrI64(toI64(req)), C.int32_t(maxPodsPerNode), ptrI32(b.idx[:p]),
+		ptrI64(b.score[:p]), ptrI32(b.status[:p]), nil, nil); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_schedule_sequential_balanced", rc)
+	}
+	return x.results(b), nil
+}
+
+// ScheduleSequentialBalancedDevice is the asynchronous form over device pointers
+// (msh_schedule_sequential_balanced_device); as ScheduleSequentialSoftDevice.
+func (x *Ctx) ScheduleSequentialBalancedDevice(p int, dPodDigit, dPodTol, dGroup, dClass unsafe.Pointer, nres int,
+	dReq unsafe.Pointer, maxPodsPerNode int32, dIdx, dScore, dStatus, stream unsafe.Pointer) error {
+	if rc := C.msh_schedule_sequential_balanced_device(x.c, C.int32_t(p), (*C.int8_t)(dPodDigit), (*C.uint8_t)(dPodTol),
+		(*C.int32_t)(dGroup), (*C.int32_t)(dClass), C.int32_t(nres), (*C.int64_t)(dReq), C.int32_t(maxPodsPerNode),
+		(*C.int32_t)(dIdx), (*C.int64_t)(dScore), (*C.int32_t)(dStatus), stream); rc != C.MSH_OK {
+		return x.lastErr("msh_schedule_sequential_balanced_device", rc)
+	}
+	return nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

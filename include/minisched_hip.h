@@ -717,6 +717,46 @@ int msh_schedule_sequential_soft_device(msh_ctx* ctx, int32_t p, const int8_t* d
                                         const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
                                         int64_t* d_out_score, int32_t* d_out_status, void* stream);
 
+/* NodeResourcesBalancedAllocation in sequential-commit mode (upstream v1.22, noderesources/balanced_allocation.go,
+ * the volume feature gate off; additive in ABI 8).
+ * msh_set_balanced_score: the plugin weight w_balanced in [0, 100] (else MSH_ERR_INVALID), default 0;
+ *   msh_balanced_score reads it back (out_w may be NULL).
+ * msh_schedule_sequential_balanced / _balanced_device take msh_schedule_sequential_soft's arguments and contract and
+ *   add w_balanced * BS to the total of every feasible node, for every pod (classed or not, grouped or not, with
+ *   zero requests or not). For pod j against node i, with r in {0, 1} the table's first two resources (cpu and
+ *   memory by convention):
+ *     q_r = used_r[i] + pod_req[j][r],  c_r = alloc_r[i]
+ *     f_r = c_r == 0 ? 1.0 : (double)q_r / (double)c_r;  if (f_r > 1.0) f_r = 1.0
+ *     BS  = (int64_t)((1.0 - fabs(f_0 - f_1)) * 100.0)
+ *   in IEEE double exactly as written: the conversions round to nearest even, the division, the difference, the
+ *   subtraction from 1 and the product are each rounded once, the last conversion truncates. BS is in [0, 100].
+ *   (Exact rational arithmetic gives other values: 0/1 against 4/5 is 19 here, not 20.) No default is substituted
+ *   for a zero request. The first maximum in List order wins and out_score is the total, as in _soft. The call works
+ *   in every resource score mode, MSH_RESOURCE_SCORE_NONE included.
+ *   With w_balanced == 0 the call is _soft itself, the same outputs and state. With w_balanced > 0 the checks are
+ *   those of a _soft call on a ctx with a SCHEDULE_ANYWAY group (whether or not the ctx holds one; the bounds on
+ *   counts and skews apply only if it does), and in addition:
+ *     no resource table, a table with fewer than two resources, or nres different from the table's: MSH_ERR_STATE;
+ *     an amount of the table above MSH_RESOURCE_SCORE_MAX (the ctx's bound over uploads and patches):
+ *       MSH_ERR_UNSUPPORTED; a request above it (host form): MSH_ERR_INVALID;
+ *     100 * (W_res + w_affinity + w_taint + w_spread + w_balanced) > 65,534: MSH_ERR_UNSUPPORTED;
+ *     a table above msh_seq_balanced_max_nodes(nres): MSH_ERR_UNSUPPORTED.
+ *   Random tie-break and score-column plugin lists are refused as in _soft. A failed call changes nothing.
+ * Node limits: msh_seq_balanced_max_nodes, _soft's limits (4,096 nodes up to two resources, 2,048 above).
+ * No other entry point reads w_balanced. */
+int msh_set_balanced_score(msh_ctx* ctx, int32_t w_balanced);
+int msh_balanced_score(const msh_ctx* ctx, int32_t* out_w);
+int msh_seq_balanced_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t* out_max_nodes);
+int msh_schedule_sequential_balanced(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                     const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                     const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                     int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_balanced_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit,
+                                            const uint8_t* d_pod_tol, const int32_t* d_pod_group,
+                                            const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
+                                            int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
+                                            int32_t* d_out_status, void* stream);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

@@ -92,6 +92,8 @@ EXPORTED = (
     "msh_set_spread_group_modes", "msh_get_spread_group_modes", "msh_set_spread_score_weight", "msh_spread_score_weight",
     "msh_spread_soft_weight", "msh_seq_soft_max_nodes", "msh_schedule_sequential_soft",
     "msh_schedule_sequential_soft_device",
+    "msh_set_balanced_score", "msh_balanced_score", "msh_seq_balanced_max_nodes", "msh_schedule_sequential_balanced",
+    "msh_schedule_sequential_balanced_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -247,6 +249,11 @@ _SIGS = {
     "msh_seq_soft_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_schedule_sequential_soft": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
     "msh_schedule_sequential_soft_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "msh_set_balanced_score": (C.c_int, [_P, _I32]),
+    "msh_balanced_score": (C.c_int, [_P, C.POINTER(_I32)]),
+    "msh_seq_balanced_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
+    "msh_schedule_sequential_balanced": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_balanced_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

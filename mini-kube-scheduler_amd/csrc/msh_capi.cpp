@@ -2603,7 +2603,7 @@ int32_t prefs_classes(const msh_ctx* c) { return c->have_prefs ? c->pref_classes
 // (the class column is not required by itself), with the preference kernel's table limits, then the two of this
 // call: pod classes with neither column (and columns of unequal C), and a weighted sum the packed key cannot hold.
 int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node, bool grouped,
-                bool classed, bool soft_entry = false) {
+                bool classed, bool soft_entry = false, bool balanced = false) {
   if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
   if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
   int rc = soft_entry ? MSH_OK : refuse_soft_groups(c, entry, grouped);
@@ -2613,6 +2613,15 @@ int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t 
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
   if (grouped && !c->have_zone) return fail(c, MSH_ERR_STATE, "msh_upload_node_zones has not been called");
+  if (balanced) {  // the balanced score reads the table's first two resources in every resource score mode
+    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
+    if (c->nres < 2)
+      return fail(c, MSH_ERR_STATE, "the balanced score needs a resource table with at least two resources, the "
+                                    "table has " + std::to_string(c->nres));
+    if (nres != c->nres)
+      return fail(c, MSH_ERR_STATE, "the balanced score needs the requests of all " + std::to_string(c->nres) +
+                                        " resources of the table, the call has " + std::to_string(nres));
+  }
   if (nres) {
     if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
     if (nres != c->nres)
@@ -2625,12 +2634,19 @@ int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t 
       return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
                                         " resources, the call has " + std::to_string(nres));
   }
-  const int32_t lim = soft_entry ? msh::seq_soft_max_nodes(nres) : msh::seq_prefs_max_nodes(nres);
+  const int32_t lim = balanced ? msh::seq_balanced_max_nodes(nres)
+                               : (soft_entry ? msh::seq_soft_max_nodes(nres) : msh::seq_prefs_max_nodes(nres));
   if (c->n_nodes > lim)
-    return fail(c, MSH_ERR_UNSUPPORTED, msh::seq_table_limit_message(soft_entry ? "soft-spread" : "preference", lim, nres));
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                msh::seq_table_limit_message(balanced ? "balanced-allocation" : (soft_entry ? "soft-spread" : "preference"),
+                                             lim, nres));
   if (scored && c->res_max > MSH_RESOURCE_SCORE_MAX)
     return fail(c, MSH_ERR_UNSUPPORTED,
                 "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
+                "or patch wrote " + std::to_string(c->res_max));
+  if (balanced && c->res_max > MSH_RESOURCE_SCORE_MAX)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "the balanced score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
                 "or patch wrote " + std::to_string(c->res_max));
   if (classed && !c->have_class && !c->have_prefs)
     return fail(c, MSH_ERR_STATE, "pod classes with neither msh_upload_node_class_prefs nor msh_upload_node_class_bits");
@@ -2647,7 +2663,12 @@ int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t 
     return fail(c, MSH_ERR_UNSUPPORTED,
                 "the weights of the resource score, the two preference scores and the spread score sum to " +
                     std::to_string(wsum + c->w_spread) + ": the packed key holds 100 x 655 at most");
-  if (grouped) {
+  if (balanced && 100 * (wsum + c->w_spread + c->w_balanced) > 65534)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                "the weights of the resource score, the two preference scores, the spread score and the balanced score "
+                "sum to " + std::to_string(wsum + c->w_spread + c->w_balanced) + ": the packed key holds 100 x 655 at most");
+  // the counts' bounds belong to the soft groups' term: a balanced call on a ctx without one runs none of it
+  if (grouped && (!balanced || c->sp_soft > 0)) {
     if (c->sp_cnt_bound > MSH_SPREAD_SOFT_MAX)
       return fail(c, MSH_ERR_UNSUPPORTED, "a spread count may have reached " + std::to_string(c->sp_cnt_bound) +
                                               ", above MSH_SPREAD_SOFT_MAX = 2^24 (msh_reset_spread_counts zeroes them)");
@@ -2681,21 +2702,24 @@ int soft_weights_device(msh_ctx* c) {
 int prefs_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
                  const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
                  int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
-                 void* stream, bool soft = false) {
+                 void* stream, bool soft = false, bool balanced = false) {
   c->err.clear();
   if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // group, class and score optional
     return fail(c, MSH_ERR_INVALID, "null device pointer");
   if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr, soft);
+  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr, soft,
+                       balanced);
   if (rc != MSH_OK) return rc;
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   static_assert(msh::SPREAD_SOFT_MAX == MSH_SPREAD_SOFT_MAX, "the kernel's bound is the header's");
-  if (d_pod_class && (rc = prefs_table(c, soft ? msh::seq_soft_npl(nres) : msh::seq_prefs_npl(nres))) != MSH_OK) return rc;
-  if (soft && (rc = soft_weights_device(c)) != MSH_OK) return rc;
-  msh::SoftArgs so{};
+  const int32_t npl = balanced ? msh::seq_balanced_npl(nres) : (soft ? msh::seq_soft_npl(nres) : msh::seq_prefs_npl(nres));
+  if (d_pod_class && (rc = prefs_table(c, npl)) != MSH_OK) return rc;
+  if (soft && (!balanced || c->sp_soft > 0) && (rc = soft_weights_device(c)) != MSH_OK) return rc;
+  msh::BalancedArgs ba{};
+  msh::SoftArgs& so = ba.so;
   msh::PrefArgs& pa = so.p;
   pa.ss.s = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
                         d_out_score, d_out_status);
@@ -2719,14 +2743,15 @@ int prefs_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_d
         if (c->h_spmode[(size_t)k] == MSH_SPREAD_SCHEDULE_ANYWAY) so.soft[k >> 6] |= uint64_t(1) << (k & 63);
       so.w_spread = (uint32_t)c->w_spread;
       so.zone_weight = c->d_zone_weight;
-      e = msh::launch_seq_soft(so, s, &err);
+      ba.w_balanced = (uint32_t)c->w_balanced;
+      e = balanced ? msh::launch_seq_balanced(ba, s, &err) : msh::launch_seq_soft(so, s, &err);
     } else {
       e = msh::launch_seq_prefs(pa, s, &err);
     }
   }
   if (e != hipSuccess) {
     if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
-    return hip_fail(c, e, soft ? "seq_soft_kernel" : "seq_prefs_kernel");
+    return hip_fail(c, e, balanced ? "seq_balanced_kernel" : (soft ? "seq_soft_kernel" : "seq_prefs_kernel"));
   }
   c->counts_dirty = false;  // the one workgroup folded the replicas
   spread_bound_add(c, d_pod_group != nullptr, p);
@@ -2748,16 +2773,16 @@ int msh_schedule_sequential_prefs_device(msh_ctx* c, int32_t p, const int8_t* d_
 
 namespace {
 // msh_schedule_sequential_prefs with a nonzero preference weight, and msh_schedule_sequential_soft on a ctx with a
-// SCHEDULE_ANYWAY group (soft)
+// SCHEDULE_ANYWAY group (soft), and msh_schedule_sequential_balanced with a nonzero weight (soft and balanced)
 int prefs_host(msh_ctx* c, const char* entry, bool soft, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
                const int32_t* pod_group, const int32_t* pod_class, int32_t nres, const int64_t* pod_req,
                int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score, int32_t* out_status,
-               msh_commit_cb commit_cb, void* user) {
+               msh_commit_cb commit_cb, void* user, bool balanced = false) {
   c->err.clear();
   if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // group, class and score optional
     return fail(c, MSH_ERR_INVALID, "null host pointer");
   if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
-  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr, soft);
+  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr, soft, balanced);
   if (rc != MSH_OK) return rc;
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
   const int32_t C = prefs_classes(c);
@@ -2775,6 +2800,9 @@ int prefs_host(msh_ctx* c, const char* entry, bool soft, int32_t p, const int8_t
     if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
       return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
                                           std::to_string(e % (size_t)p));
+    if (balanced && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
+      return fail(c, MSH_ERR_INVALID, "the balanced score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
+                                          std::to_string(e % (size_t)p));
   }
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
@@ -2790,7 +2818,7 @@ int prefs_host(msh_ctx* c, const char* entry, bool soft, int32_t p, const int8_t
   if (pod_class) std::memcpy(sc, pod_class, cbytes);
   rc = prefs_device(c, entry, p, io.d_pd, io.d_pt, pod_group ? sg : nullptr, pod_class ? sc : nullptr, nres,
                     reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
-                    io.o_status, c->stream, soft);
+                    io.o_status, c->stream, soft, balanced);
   if (rc != MSH_OK) return rc;
   if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
   if (commit_cb)
@@ -2842,6 +2870,52 @@ int msh_schedule_sequential_soft(msh_ctx* c, int32_t p, const int8_t* pod_digit,
                                          max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
   return prefs_host(c, "msh_schedule_sequential_soft", true, p, pod_digit, pod_tol, pod_group, pod_class, nres,
                     pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+}
+
+// NodeResourcesBalancedAllocation. With w_balanced == 0 there is nothing to add to any pod: the call is _soft itself.
+// With a nonzero weight every pod has the term, so the balanced kernel runs whatever the ctx's groups are.
+int msh_set_balanced_score(msh_ctx* c, int32_t w_balanced) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (w_balanced < 0 || w_balanced > 100) return fail(c, MSH_ERR_INVALID, "balanced score weight outside [0, 100]");
+  c->w_balanced = w_balanced;
+  return MSH_OK;
+}
+
+int msh_balanced_score(const msh_ctx* c, int32_t* out_w) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_w) *out_w = c->w_balanced;
+  return MSH_OK;
+}
+
+int msh_seq_balanced_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = msh::seq_balanced_max_nodes(nres);
+  return MSH_OK;
+}
+
+int msh_schedule_sequential_balanced_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                                            const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
+                                            const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
+                                            int64_t* d_out_score, int32_t* d_out_status, void* stream) {
+  if (!c) return MSH_ERR_INVALID;
+  if (c->w_balanced == 0)
+    return msh_schedule_sequential_soft_device(c, p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class, nres, d_pod_req,
+                                               max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
+  return prefs_device(c, "msh_schedule_sequential_balanced_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
+                      nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, true, true);
+}
+
+int msh_schedule_sequential_balanced(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                     const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
+                                     const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
+                                     int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
+  if (!c) return MSH_ERR_INVALID;
+  if (c->w_balanced == 0)
+    return msh_schedule_sequential_soft(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
+                                        max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
+  return prefs_host(c, "msh_schedule_sequential_balanced", true, p, pod_digit, pod_tol, pod_group, pod_class, nres,
+                    pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user, true);
 }
 
 int msh_keys_slot1_is_any(const msh_ctx* c, int32_t* out_flag) {

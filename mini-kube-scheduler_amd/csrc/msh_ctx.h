@@ -125,6 +125,8 @@ struct msh_ctx {
   int32_t w_spread = 0;
   int64_t sp_cnt_bound = 0;
   double* d_zone_weight = nullptr;
+  // NodeResourcesBalancedAllocation (msh_schedule_sequential_balanced): the plugin weight, 0 = the call is _soft
+  int32_t w_balanced = 0;
   // the per-class node masks (msh_upload_node_class_bits), unversioned like the capacity column: class_cap uint64
   // on the device (the padding slots 0), the host copy (n_nodes words, what msh_node_class_bits returns) and the
   // number of classes C the column was uploaded for; dropped by msh_upload_nodes. Only

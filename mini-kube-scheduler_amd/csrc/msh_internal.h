@@ -389,6 +389,20 @@ struct SoftArgs {
 int32_t seq_soft_max_nodes(int32_t nres);
 int32_t seq_soft_npl(int32_t nres);
 hipError_t launch_seq_soft(const SoftArgs& a, hipStream_t s, std::string* err);
+// The balanced-allocation form (msh_seq_balanced.hip, msh_schedule_sequential_balanced with a nonzero w_balanced):
+// the soft-spread form with w_balanced * BS added to every feasible node's total, BS upstream's
+// NodeResourcesBalancedAllocation score of the table's first two resources, evaluated in IEEE double. so.soft may be
+// all zero (no SCHEDULE_ANYWAY group; so.zone_weight may then be null). so.p.ss.s.f.nres is 2..FIT_MAX_RES,
+// 100 * (so.p.ss.weight + so.p.w_aff + so.p.w_taint + so.w_spread + w_balanced) must be <= 65,534 and every amount
+// <= 2^55 in every resource score mode (checked on the host).
+struct BalancedArgs {
+  SoftArgs so;
+  uint32_t w_balanced;  // the weight, [1, 100]
+};
+// Nodes the balanced-allocation kernel holds: the soft-spread kernel's.
+int32_t seq_balanced_max_nodes(int32_t nres);
+int32_t seq_balanced_npl(int32_t nres);
+hipError_t launch_seq_balanced(const BalancedArgs& a, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

@@ -707,7 +707,7 @@ class DeviceContext:
                                 max_pods_per_node, on_commit, out)
 
     def _prefs_call(self, name, pod_digit, pod_tol, pod_group, pod_class, pod_req, max_pods_per_node, on_commit, out):
-        """schedule_sequential_prefs and schedule_sequential_soft: the same arguments, msh_<name>."""
+        """schedule_sequential_prefs, _soft and _balanced: the same arguments, msh_<name>."""
         pod_digit = np.ascontiguousarray(pod_digit, np.int8)
         pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
         cols = [pod_digit, pod_tol]
@@ -787,6 +787,39 @@ class DeviceContext:
                                         d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_soft_device (asynchronous on `stream`; as schedule_sequential_prefs_device)."""
         self._check(self._lib.msh_schedule_sequential_soft_device(
+            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
+            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+
+    # -- NodeResourcesBalancedAllocation --
+    def set_balanced_score(self, weight: int = 0) -> None:
+        """msh_set_balanced_score: the plugin weight of the balanced-allocation score, in [0, 100]."""
+        self._check(self._lib.msh_set_balanced_score(self.handle, int(weight)))
+
+    def balanced_score(self) -> int:
+        w = C.c_int32()
+        self._check(self._lib.msh_balanced_score(self.handle, C.byref(w)))
+        return w.value
+
+    def seq_balanced_max_nodes(self, nres: int = 0) -> int:
+        """msh_seq_balanced_max_nodes: the largest table schedule_sequential_balanced takes with nres (0..4) resources."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_balanced_max_nodes(self.handle, int(nres), C.byref(out)))
+        return out.value
+
+    def schedule_sequential_balanced(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_group=None, pod_class=None,
+                                     pod_req=None, max_pods_per_node: int = 0,
+                                     on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_balanced: schedule_sequential_soft with w_balanced * BS added to every feasible
+        node's total, BS upstream's NodeResourcesBalancedAllocation score of the table's first two resources after
+        the pod, evaluated in float64 as upstream does. With the weight 0 it is schedule_sequential_soft."""
+        return self._prefs_call("schedule_sequential_balanced", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                max_pods_per_node, on_commit, out)
+
+    def schedule_sequential_balanced_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
+                                            d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
+                                            d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
+        """msh_schedule_sequential_balanced_device (asynchronous on `stream`; as schedule_sequential_soft_device)."""
+        self._check(self._lib.msh_schedule_sequential_balanced_device(
             self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
             d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
 
@@ -1012,6 +1045,11 @@ class Scheduler:
     (constraints.preferred_affinity_score, constraints.prefer_no_schedule_count) is nonzero on some node, both
     columns are uploaded for the same classes, and a call in which some pod has such a preference is made with
     DeviceContext.schedule_sequential_prefs; every other call takes the paths above.
+
+    balanced_allocation_weight (in [0, 100], default 0) is NodeResourcesBalancedAllocation's plugin weight. It needs
+    `resources` with at least two names, the first two being the ones upstream balances (cpu and memory). With a
+    nonzero weight every schedule_sequential call is DeviceContext.schedule_sequential_balanced, with the classes,
+    groups and requests that the paths above would have passed.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
@@ -1020,8 +1058,15 @@ class Scheduler:
                  device: int = 0, ctx: DeviceContext | None = None, *, tie_break="first", tie_seed: int = 0,
                  resources: Sequence[str] | None = None, resource_score=None, resource_score_weight: int = 1,
                  resource_weights=None, zones: str | None = None, spread_groups: Mapping[str, int] | None = None,
-                 spread_label: str = "app", preferred_affinity_weight: int = 0, prefer_no_schedule_weight: int = 0):
+                 spread_label: str = "app", preferred_affinity_weight: int = 0, prefer_no_schedule_weight: int = 0,
+                 balanced_allocation_weight: int = 0):
         self.resources = None if resources is None else tuple(resources)
+        w = balanced_allocation_weight
+        if isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= 100:
+            raise ValueError("balanced_allocation_weight: an integer in [0, 100]")
+        if w and (resources is None or len(self.resources) < 2):
+            raise ValueError("balanced_allocation_weight needs resources with at least two names (cpu and memory first)")
+        self.balanced_allocation_weight = w
         for w in (preferred_affinity_weight, prefer_no_schedule_weight):
             if isinstance(w, bool) or not isinstance(w, int) or not 0 <= w <= 100:
                 raise ValueError("preferred_affinity_weight / prefer_no_schedule_weight: integers in [0, 100]")
@@ -1073,6 +1118,8 @@ class Scheduler:
         self._class_prefers: set[int] = set()
         if self._prefs_on:
             self.ctx.set_preference_weights(preferred_affinity_weight, prefer_no_schedule_weight)
+        if self.balanced_allocation_weight:
+            self.ctx.set_balanced_score(self.balanced_allocation_weight)
         self._tainted: bool | None = None  # a node of the snapshot has a NoSchedule / NoExecute taint (None: not looked yet)
 
     @staticmethod
@@ -1160,6 +1207,8 @@ class Scheduler:
             self.ctx.upload_node_capacity(self.nodes.allocatable_pods)
             self._cap_synced = True
         classes = self.pod_class_ids(pods)
+        if self.balanced_allocation_weight:  # every pod has the balanced term: one call, whatever else is configured
+            return self._schedule_balanced(pods, table, classes, max_pods_per_node)
         if (classes >= 0).any():  # a pod that some node does not admit: the class call, whatever else is configured
             return self._schedule_classes(pods, table, classes, max_pods_per_node)
         if self.resources is None and self.zones is None:
@@ -1276,6 +1325,22 @@ class Scheduler:
             return self._results(table, idx, score, status)
         idx, score, status = self.ctx.schedule_sequential_classes(table.digit, table.tolerates, groups, classes, req,
                                                                   max_pods_per_node)
+        return self._results(table, idx, score, status)
+
+    def _schedule_balanced(self, pods, table, classes, max_pods_per_node: int) -> list[ScheduleResult]:
+        """DeviceContext.schedule_sequential_balanced with whatever the scheduler is configured with: the class
+        columns if some pod of the snapshot has a class, the groups with zones, the requests always."""
+        req = self._sync_spread_inputs(pods)
+        classed = bool(self._class_masks)
+        if classed and not self._class_synced:
+            self.ctx.upload_node_class_bits(len(self._class_masks), self.node_class_bits())
+            if self._prefs_on:  # both columns, for the same classes
+                self.ctx.upload_node_class_prefs(len(self._class_masks), np.array(self._class_aff, np.uint16),
+                                                 np.array(self._class_pns, np.uint16))
+            self._class_synced = True
+        groups = self.pod_group_ids(pods) if self.zones is not None else None
+        idx, score, status = self.ctx.schedule_sequential_balanced(table.digit, table.tolerates, groups,
+                                                                   classes if classed else None, req, max_pods_per_node)
         return self._results(table, idx, score, status)
 
     def _schedule_spread(self, pods, table, max_pods_per_node: int) -> list[ScheduleResult]:
