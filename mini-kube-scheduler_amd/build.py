@@ -43,6 +43,7 @@ SOURCES = [
     ("msh_seq_balanced.hip", "hipcc", ["-x", "hip"]),
     ("msh_prep.hip", "hipcc", ["-x", "hip"]),
     ("msh_capi.cpp", "hipcc", []),
+    ("msh_capi_seq.cpp", "hipcc", []),
     ("msh_shard.cpp", "hipcc", []),
     ("msh_pack.cpp", "g++", []),
 ]

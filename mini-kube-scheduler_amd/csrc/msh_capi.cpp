@@ -1,4 +1,5 @@
-// msh_capi.cpp — implementation of include/minisched_hip.h (the drop-in C-ABI).
+// msh_capi.cpp — implementation of include/minisched_hip.h (the drop-in C-ABI), but for the grouped sequential-commit
+// entry points (msh_capi_seq.cpp) and the node-sharded ones (msh_shard.cpp).
 //
 // One msh_ctx per device. The ctx owns the device-resident node table (the replacement for
 // the per-cycle Nodes().List at minisched/minisched.go:40), the plugin descriptor
@@ -242,6 +243,49 @@ int track_launch(msh_ctx* c, hipStream_t s, bool seq) {
 int after_seq(msh_ctx* c) {
   for (auto& e : c->seq_inflight) MSH_HIP(c, hipStreamWaitEvent(c->prep_stream, e.second, 0));
   return MSH_OK;
+}
+
+int seq_serialize(msh_ctx* c, hipStream_t s) {
+  for (auto& ev : c->seq_inflight)
+    if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
+  return MSH_OK;
+}
+
+void seq_args_fill(msh_ctx* c, msh::SeqArgs& a, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                   int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status) {
+  a.planes = cur_table(c).d_planes;
+  a.n_words = c->n_pad / 32;
+  a.n_nodes = c->n_nodes;
+  a.pod_digit = d_pod_digit;
+  a.pod_tol = d_pod_tol;
+  a.n_pods = p;
+  a.pp = c->pp;
+  a.cap = c->have_cap ? c->d_cap : nullptr;
+  a.counts = c->d_counts;
+  a.count_stride = (int64_t)c->counts_cap;
+  a.count_replicas = c->counts_replicas;
+  a.out_idx = d_out_idx;
+  a.out_score = d_out_score;
+  a.out_status = d_out_status;
+}
+
+int check_requests(msh_ctx* c, int32_t nres, int32_t p, const int64_t* pod_req, bool scored, bool balanced) {
+  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
+    if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
+      return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
+    if ((scored || balanced) && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
+      return fail(c, MSH_ERR_INVALID, std::string(scored ? "a resource score" : "the balanced score") +
+                                          " needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
+                                          std::to_string(e % (size_t)p));
+  }
+  return MSH_OK;
+}
+
+void commit_callbacks(msh_commit_cb cb, void* user, int32_t p, const int32_t* out_idx, const int64_t* out_score,
+                      const int32_t* out_status) {
+  if (!cb) return;
+  for (int32_t j = 0; j < p; j++)
+    if (out_status[j] == MSH_PLACED) cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
 }
 
 // The page-locked node staging buffer, at least `bytes` long. Every rewrite finishes its copies
@@ -1243,22 +1287,11 @@ int seq_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_dig
   if ((rc = ready(c)) != MSH_OK) return rc;
   if (fit.nres && (rc = fit_check(c, fit.nres)) != MSH_OK) return rc;
   msh::SeqArgs a{};
-  const NodeTable& t = cur_table(c);
-  a.planes = t.d_planes;
-  a.n_words = c->n_pad / 32;
-  a.n_nodes = c->n_nodes;
-  a.pod_digit = d_pod_digit;
-  a.pod_tol = d_pod_tol;
-  a.n_pods = p;
-  a.pp = c->pp;
+  seq_args_fill(c, a, p, d_pod_digit, d_pod_tol, d_out_idx, d_out_score, d_out_status);
   // a capacity column: the in-order capacity form with min(cap[i], max_pods_per_node) per node (no scalar:
   // the column alone)
   const bool node_cap = c->have_cap;
   a.max_pods = node_cap && max_pods_per_node == 0 ? INT32_MAX : max_pods_per_node;
-  a.cap = node_cap ? c->d_cap : nullptr;
-  a.counts = c->d_counts;
-  a.count_stride = (int64_t)c->counts_cap;
-  a.count_replicas = c->counts_replicas;
   // Without a capacity no commit feeds a later decision (the counts are read by nothing the plugins
   // score): the default runs the per-pair batch kernel with the commit epilogue (pair_kernel<CNT>, every
   // placed pod's count added to a replica), whose placements are msh_schedule_batch's; seq_split = 2 keeps
@@ -1269,14 +1302,7 @@ int seq_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_dig
   const bool split = !fit.nres && (pair_form || msh::seq_blocks(a, c->dev) > 1);
   if (fit.nres && a.max_pods == 0) a.max_pods = INT32_MAX;
   a.fold = !split && c->counts_dirty ? 1 : 0;
-  // one sequential launch of a ctx at a time: each commits into (and a fold rewrites) the same counts,
-  // so this stream first waits for the ctx's sequential launches in flight on other streams
-  if (p > 0)
-    for (auto& ev : c->seq_inflight)
-      if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
-  a.out_idx = d_out_idx;
-  a.out_score = d_out_score;
-  a.out_status = d_out_status;
+  if (p > 0 && (rc = seq_serialize(c, s)) != MSH_OK) return rc;
   std::string err;
   hipError_t e;
   if (pair_form) {
@@ -1299,11 +1325,7 @@ int seq_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_dig
     if (c->rs_mode != MSH_RESOURCE_SCORE_NONE) {
       msh::FitScoreArgs sa{};
       sa.f = f;
-      sa.most = c->rs_mode == MSH_RESOURCE_SCORE_MOST_ALLOCATED ? 1 : 0;
-      sa.weight = c->rs_weight;
-      uint32_t sum = 0;
-      for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(sa.rw[r] = r < fit.nres ? c->rs_w[r] : 0);
-      sa.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
+      resource_score_setting(c, fit.nres, sa);
       e = msh::launch_seq_score(sa, s, &err);
     } else {
       e = msh::launch_seq_fit(f, s, &err);
@@ -1337,14 +1359,7 @@ int seq_host(msh_ctx* c, const char* entry, int32_t p, const int8_t* pod_digit, 
     if (max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
     if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
     if ((rc = fit_check(c, nres)) != MSH_OK) return rc;
-    const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-    for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
-      if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
-        return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
-      if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
-        return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
-                                            std::to_string(e % (size_t)p));
-    }
+    if ((rc = check_requests(c, nres, p, pod_req, c->rs_mode != MSH_RESOURCE_SCORE_NONE, false)) != MSH_OK) return rc;
   }
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
@@ -1365,9 +1380,7 @@ int seq_host(msh_ctx* c, const char* entry, int32_t p, const int8_t* pod_digit, 
                   c->stream);
   if (rc != MSH_OK) return rc;
   if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  if (commit_cb)
-    for (int32_t j = 0; j < p; j++)
-      if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
+  commit_callbacks(commit_cb, user, p, out_idx, out_score, out_status);
   return MSH_OK;
 }
 }  // namespace
@@ -1687,1235 +1700,6 @@ int msh_node_resources(msh_ctx* c, int32_t* out_nres, int64_t* out_alloc, int64_
   }
   MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
   return MSH_OK;
-}
-
-// Topology spread (msh_schedule_sequential_spread): the zone column, the groups and the counts cnt[g][z]. None of
-// it is versioned; the writers and readers go through prep_stream behind the sequential launches in flight, which
-// read all of it at their start and write the counts at their end, and finish before they return.
-namespace {
-constexpr size_t SPREAD_CNT_BYTES = (size_t)MSH_MAX_SPREAD_GROUPS * MSH_MAX_ZONES * sizeof(int32_t);
-
-// d_skew and d_spread_cnt: allocated whole and zeroed at first use
-int spread_alloc(msh_ctx* c) {
-  if (!c->d_skew) MSH_HIP(c, hipMalloc(&c->d_skew, MSH_MAX_SPREAD_GROUPS * sizeof(int32_t)));
-  if (c->d_spread_cnt) return MSH_OK;
-  int32_t* cn = nullptr;
-  MSH_HIP(c, hipMalloc(&cn, SPREAD_CNT_BYTES));
-  hipError_t e = hipMemsetAsync(cn, 0, SPREAD_CNT_BYTES, c->prep_stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->prep_stream);
-  if (e != hipSuccess) {
-    (void)hipFree(cn);
-    return hip_fail(c, e, "spread counts");
-  }
-  c->d_spread_cnt = cn;
-  return MSH_OK;
-}
-
-int spread_zero_counts(msh_ctx* c) {
-  MSH_HIP(c, hipMemsetAsync(c->d_spread_cnt, 0, SPREAD_CNT_BYTES, c->prep_stream));
-  c->sp_cnt_bound = 0;
-  return MSH_OK;
-}
-
-// A call that takes pod groups on a ctx with a SCHEDULE_ANYWAY group is msh_schedule_sequential_soft's alone: the
-// other entry points would run the group's pods through the hard filter. An explicit error, never a fallback.
-int refuse_soft_groups(msh_ctx* c, const char* entry, bool grouped) {
-  if (!grouped || c->sp_soft == 0) return MSH_OK;
-  return fail(c, MSH_ERR_UNSUPPORTED,
-              std::string(entry) + ": the ctx holds " + std::to_string(c->sp_soft) +
-                  " SCHEDULE_ANYWAY spread group(s) (msh_set_spread_group_modes); a call with pod groups must be "
-                  "msh_schedule_sequential_soft");
-}
-
-// p pods went to a launch with groups: each may have raised one count by one (sp_cnt_bound)
-void spread_bound_add(msh_ctx* c, bool grouped, int32_t p) {
-  if (grouped) c->sp_cnt_bound += p;
-}
-}  // namespace
-
-int msh_upload_node_zones(msh_ctx* c, int32_t n, const int32_t* zone) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (n != c->n_nodes)
-    return fail(c, MSH_ERR_INVALID, "zone column of " + std::to_string(n) + " entries for " +
-                                        std::to_string(c->n_nodes) + " uploaded nodes");
-  if (n > 0 && !zone) return fail(c, MSH_ERR_INVALID, "null zone array");
-  uint64_t zset = 0;
-  for (int32_t i = 0; i < n; ++i) {
-    if (zone[i] < -1 || zone[i] >= MSH_MAX_ZONES)
-      return fail(c, MSH_ERR_INVALID, "zone outside [-1, MSH_MAX_ZONES) at node " + std::to_string(i));
-    if (zone[i] >= 0) zset |= uint64_t(1) << zone[i];
-  }
-  DeviceGuard g(c->device);
-  int rc = spread_alloc(c);
-  if (rc != MSH_OK) return rc;
-  if ((size_t)c->n_pad > c->zone_cap) {
-    int32_t* dz = nullptr;
-    MSH_HIP(c, hipMalloc(&dz, (size_t)c->n_pad * sizeof(int32_t)));
-    wait_events(c->seq_inflight);
-    (void)hipFree(c->d_zone);
-    c->d_zone = dz;
-    c->zone_cap = (size_t)c->n_pad;
-    c->have_zone = false;
-  }
-  if ((rc = after_seq(c)) != MSH_OK) return rc;
-  const size_t bytes = (size_t)c->n_pad * sizeof(int32_t);
-  if ((rc = node_stage(c, bytes)) != MSH_OK) return rc;
-  c->have_zone = false;  // a failed copy leaves no column
-  int32_t* st = reinterpret_cast<int32_t*>(c->h_nstage);
-  std::fill(st, st + c->n_pad, -1);  // the padding slots never hold a node
-  if (n > 0) std::copy(zone, zone + n, st);
-  MSH_HIP(c, hipMemcpyAsync(c->d_zone, st, bytes, hipMemcpyHostToDevice, c->prep_stream));
-  if ((rc = spread_zero_counts(c)) != MSH_OK) return rc;  // a node's zone changed under its pods
-  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
-  c->h_zone.assign(zone, zone + n);
-  c->zset = zset;
-  c->have_zone = true;
-  return MSH_OK;
-}
-
-int msh_clear_node_zones(msh_ctx* c) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  c->have_zone = false;  // launches in flight keep reading the device column, which stays allocated
-  c->h_zone.clear();
-  c->zset = 0;
-  return MSH_OK;
-}
-
-int msh_node_zones(const msh_ctx* c, int32_t* out_zone, int32_t* out_present) {
-  if (!c || !out_present) return MSH_ERR_INVALID;
-  *out_present = c->have_zone ? 1 : 0;
-  if (c->have_zone && out_zone) std::copy(c->h_zone.begin(), c->h_zone.end(), out_zone);
-  return MSH_OK;
-}
-
-int msh_set_spread_groups(msh_ctx* c, int32_t G, const int32_t* max_skew) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (G < 0 || G > MSH_MAX_SPREAD_GROUPS) return fail(c, MSH_ERR_INVALID, "G outside [0, MSH_MAX_SPREAD_GROUPS]");
-  if (G > 0 && !max_skew) return fail(c, MSH_ERR_INVALID, "null max_skew array");
-  for (int32_t k = 0; k < G; ++k)
-    if (max_skew[k] < 1) return fail(c, MSH_ERR_INVALID, "max_skew below 1 at group " + std::to_string(k));
-  DeviceGuard g(c->device);
-  int rc = spread_alloc(c);
-  if (rc != MSH_OK) return rc;
-  if ((rc = after_seq(c)) != MSH_OK) return rc;
-  if (G > 0) {
-    if ((rc = node_stage(c, (size_t)G * sizeof(int32_t))) != MSH_OK) return rc;
-    std::memcpy(c->h_nstage, max_skew, (size_t)G * sizeof(int32_t));
-    MSH_HIP(c, hipMemcpyAsync(c->d_skew, c->h_nstage, (size_t)G * sizeof(int32_t), hipMemcpyHostToDevice,
-                              c->prep_stream));
-  }
-  if (G != c->sp_groups && (rc = spread_zero_counts(c)) != MSH_OK) return rc;  // the rows mean other groups now
-  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
-  if (G != c->sp_groups) {  // other groups: every mode back to the default
-    c->h_spmode.assign((size_t)G, (uint8_t)MSH_SPREAD_DO_NOT_SCHEDULE);
-    c->sp_soft = 0;
-  }
-  c->sp_groups = G;
-  c->h_skew.assign(max_skew, max_skew + G);
-  return MSH_OK;
-}
-
-int msh_set_spread_group_modes(msh_ctx* c, int32_t G, const uint8_t* mode) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (G != c->sp_groups)
-    return fail(c, MSH_ERR_INVALID, "modes for " + std::to_string(G) + " groups, msh_set_spread_groups set " +
-                                        std::to_string(c->sp_groups));
-  if (G > 0 && !mode) return fail(c, MSH_ERR_INVALID, "null mode array");
-  int32_t soft = 0;
-  for (int32_t k = 0; k < G; ++k) {
-    if (mode[k] > MSH_SPREAD_SCHEDULE_ANYWAY)
-      return fail(c, MSH_ERR_INVALID, "mode above MSH_SPREAD_SCHEDULE_ANYWAY at group " + std::to_string(k));
-    soft += mode[k] == MSH_SPREAD_SCHEDULE_ANYWAY ? 1 : 0;
-  }
-  c->h_spmode.assign(mode, mode + G);  // host only: a launch takes the modes as kernel arguments
-  c->sp_soft = soft;
-  return MSH_OK;
-}
-
-int msh_get_spread_group_modes(const msh_ctx* c, int32_t* out_G, uint8_t* out_mode) {
-  if (!c) return MSH_ERR_INVALID;
-  if (out_G) *out_G = c->sp_groups;
-  if (out_mode)
-    for (int32_t k = 0; k < c->sp_groups; ++k)
-      out_mode[k] = (size_t)k < c->h_spmode.size() ? c->h_spmode[(size_t)k] : (uint8_t)MSH_SPREAD_DO_NOT_SCHEDULE;
-  return MSH_OK;
-}
-
-int msh_set_spread_score_weight(msh_ctx* c, int32_t w_spread) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (w_spread < 0 || w_spread > 100) return fail(c, MSH_ERR_INVALID, "spread score weight outside [0, 100]");
-  c->w_spread = w_spread;
-  return MSH_OK;
-}
-
-int msh_spread_score_weight(const msh_ctx* c, int32_t* out_w_spread) {
-  if (!c) return MSH_ERR_INVALID;
-  if (out_w_spread) *out_w_spread = c->w_spread;
-  return MSH_OK;
-}
-
-namespace {
-// upstream's topologyNormalizingWeight for size = 0..MSH_MAX_ZONES zones, log(size + 2): this library's std::log,
-// computed once; the kernel multiplies by these values and msh_spread_soft_weight returns them
-const double* soft_weights() {
-  static const std::array<double, MSH_MAX_ZONES + 1> w = [] {
-    std::array<double, MSH_MAX_ZONES + 1> t{};
-    for (int32_t k = 0; k <= MSH_MAX_ZONES; ++k) t[(size_t)k] = std::log((double)(k + 2));
-    return t;
-  }();
-  return w.data();
-}
-}  // namespace
-
-int msh_spread_soft_weight(int32_t size, double* out) {
-  if (!out || size < 0 || size > MSH_MAX_ZONES) return MSH_ERR_INVALID;
-  *out = soft_weights()[size];
-  return MSH_OK;
-}
-
-int msh_get_spread_groups(const msh_ctx* c, int32_t* out_G, int32_t* out_max_skew) {
-  if (!c) return MSH_ERR_INVALID;
-  if (out_G) *out_G = c->sp_groups;
-  if (out_max_skew) std::copy(c->h_skew.begin(), c->h_skew.end(), out_max_skew);
-  return MSH_OK;
-}
-
-int msh_spread_counts(msh_ctx* c, int32_t* out_cnt) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (c->sp_groups == 0) return MSH_OK;
-  if (!out_cnt) return fail(c, MSH_ERR_INVALID, "null output");
-  DeviceGuard g(c->device);
-  int rc = after_seq(c);  // sequential launches of this ctx in flight update the counts
-  if (rc != MSH_OK) return rc;
-  MSH_HIP(c, hipMemcpyAsync(out_cnt, c->d_spread_cnt, (size_t)c->sp_groups * MSH_MAX_ZONES * sizeof(int32_t),
-                            hipMemcpyDeviceToHost, c->prep_stream));
-  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
-  return MSH_OK;
-}
-
-int msh_patch_spread_counts(msh_ctx* c, int32_t count, const int32_t* gi, const int32_t* zi, const int32_t* value) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
-  if (count == 0) return MSH_OK;
-  if (!gi || !zi || !value) return fail(c, MSH_ERR_INVALID, "null patch arrays");
-  std::vector<int32_t> keys((size_t)count);
-  for (int32_t k = 0; k < count; ++k) {
-    if (gi[k] < 0 || gi[k] >= c->sp_groups)
-      return fail(c, MSH_ERR_INVALID, "group outside [0, G) at patch entry " + std::to_string(k));
-    if (zi[k] < 0 || zi[k] >= MSH_MAX_ZONES)
-      return fail(c, MSH_ERR_INVALID, "zone outside [0, MSH_MAX_ZONES) at patch entry " + std::to_string(k));
-    if (value[k] < 0) return fail(c, MSH_ERR_INVALID, "negative count at patch entry " + std::to_string(k));
-    keys[(size_t)k] = gi[k] * MSH_MAX_ZONES + zi[k];
-  }
-  std::vector<int32_t> sorted(keys);
-  std::sort(sorted.begin(), sorted.end());
-  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-    return fail(c, MSH_ERR_INVALID, "duplicate (group, zone) pair");
-  DeviceGuard g(c->device);
-  int rc = after_seq(c);
-  if (rc != MSH_OK) return rc;
-  // the table (32 KB) through the page-locked stage: read, patched on the host, written back
-  if ((rc = node_stage(c, SPREAD_CNT_BYTES)) != MSH_OK) return rc;
-  int32_t* st = reinterpret_cast<int32_t*>(c->h_nstage);
-  MSH_HIP(c, hipMemcpyAsync(st, c->d_spread_cnt, SPREAD_CNT_BYTES, hipMemcpyDeviceToHost, c->prep_stream));
-  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
-  for (int32_t k = 0; k < count; ++k) st[keys[(size_t)k]] = value[k];
-  MSH_HIP(c, hipMemcpyAsync(c->d_spread_cnt, st, SPREAD_CNT_BYTES, hipMemcpyHostToDevice, c->prep_stream));
-  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
-  // the whole table is at hand: its largest count, exactly
-  c->sp_cnt_bound = *std::max_element(st, st + (size_t)c->sp_groups * MSH_MAX_ZONES);
-  return MSH_OK;
-}
-
-int msh_reset_spread_counts(msh_ctx* c) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (!c->d_spread_cnt) return MSH_OK;  // never used: nothing to zero
-  DeviceGuard g(c->device);
-  int rc = after_seq(c);
-  if (rc != MSH_OK) return rc;
-  if ((rc = spread_zero_counts(c)) != MSH_OK) return rc;
-  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
-  return MSH_OK;
-}
-
-int msh_seq_spread_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
-  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
-  *out_max_nodes = msh::seq_spread_max_nodes(nres);
-  return MSH_OK;
-}
-
-int msh_seq_spread_scored_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
-  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
-  *out_max_nodes = c->rs_mode != MSH_RESOURCE_SCORE_NONE ? msh::seq_spread_score_max_nodes(nres)
-                                                         : msh::seq_spread_max_nodes(nres);
-  return MSH_OK;
-}
-
-namespace {
-// What a _spread_scored call on a ctx with a resource score needs on top of spread_check's node, zone and table
-// checks: the setting's nres, the scored form's table limit, every written amount within MSH_RESOURCE_SCORE_MAX.
-int spread_scored_check(msh_ctx* c, int32_t nres) {
-  if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
-  if (nres != c->rs_nres)
-    return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
-                                      " resources, the call has " + std::to_string(nres));
-  if (c->n_nodes > msh::seq_spread_score_max_nodes(nres))
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                msh::seq_table_limit_message("scored topology-spread", msh::seq_spread_score_max_nodes(nres), nres));
-  if (c->res_max > MSH_RESOURCE_SCORE_MAX)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
-                "or patch wrote " + std::to_string(c->res_max));
-  return MSH_OK;
-}
-
-// What a spread call needs, checked before any device work (`entry`: the name for messages). scored_entry: the
-// call is a _spread_scored one, which takes a ctx with a resource score (spread_scored_check then follows the
-// table checks); the _spread entry points refuse such a ctx.
-int spread_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node,
-                 bool scored_entry) {
-  if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
-  if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
-  int rc = refuse_soft_groups(c, entry, true);  // a spread call always has groups
-  if (rc != MSH_OK) return rc;
-  if ((rc = refuse_random(c, entry)) != MSH_OK) return rc;
-  if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  if (scored && !scored_entry)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                std::string(entry) + ": a resource score (msh_set_resource_score) together with topology spread is "
-                                     "not implemented (MSH_RESOURCE_SCORE_NONE restores the unscored form)");
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (!c->have_zone) return fail(c, MSH_ERR_STATE, "msh_upload_node_zones has not been called");
-  if (nres) {
-    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
-    if (nres != c->nres)
-      return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
-                                          std::to_string(c->nres));
-  }
-  if (scored) return spread_scored_check(c, nres);
-  if (c->n_nodes > msh::seq_spread_max_nodes(nres))
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                msh::seq_table_limit_message("topology-spread", msh::seq_spread_max_nodes(nres), nres));
-  return MSH_OK;
-}
-
-// The argument block of the spread kernels for the ctx as it stands (the class forms take the same block: a null
-// d_pod_group then goes with no groups, and the zone column may be absent).
-msh::SpreadArgs spread_args(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                            const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req,
-                            int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
-                            int32_t* d_out_status) {
-  msh::SpreadArgs sa{};
-  msh::SeqArgs& a = sa.f.s;
-  a.planes = cur_table(c).d_planes;
-  a.n_words = c->n_pad / 32;
-  a.n_nodes = c->n_nodes;
-  a.pod_digit = d_pod_digit;
-  a.pod_tol = d_pod_tol;
-  a.n_pods = p;
-  a.pp = c->pp;
-  // the pod count limit as the resource-fit form takes it: the column and / or the scalar, or none
-  a.max_pods = max_pods_per_node == 0 ? INT32_MAX : max_pods_per_node;
-  a.cap = c->have_cap ? c->d_cap : nullptr;
-  a.counts = c->d_counts;
-  a.count_stride = (int64_t)c->counts_cap;
-  a.count_replicas = c->counts_replicas;
-  a.fold = c->counts_dirty ? 1 : 0;
-  a.out_idx = d_out_idx;
-  a.out_score = d_out_score;
-  a.out_status = d_out_status;
-  sa.f.nres = nres;
-  sa.f.res_stride = (int64_t)c->res_cap;
-  sa.f.alloc = nres ? c->d_alloc : nullptr;
-  sa.f.used = nres ? c->d_used : nullptr;
-  sa.f.pod_req = nres ? d_pod_req : nullptr;
-  sa.zone = c->have_zone ? c->d_zone : nullptr;
-  sa.pod_group = d_pod_group;
-  sa.n_groups = d_pod_group ? c->sp_groups : 0;
-  sa.max_skew = c->d_skew;
-  sa.cnt = c->d_spread_cnt;
-  sa.zset = c->have_zone ? c->zset : 0;
-  return sa;
-}
-
-// the ctx's resource score setting (mode LEAST or MOST) for a scored launch with nres resources
-void spread_score_setting(const msh_ctx* c, int32_t nres, msh::SpreadScoreArgs& ssa) {
-  ssa.most = c->rs_mode == MSH_RESOURCE_SCORE_MOST_ALLOCATED ? 1 : 0;
-  ssa.weight = c->rs_weight;
-  uint32_t sum = 0;
-  for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(ssa.rw[r] = r < nres ? c->rs_w[r] : 0);
-  ssa.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
-}
-
-int spread_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                  const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req, int32_t max_pods_per_node,
-                  int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status, void* stream, bool scored_entry) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_pod_group || !d_out_idx || !d_out_status))  // d_out_score optional
-    return fail(c, MSH_ERR_INVALID, "null device pointer");
-  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = spread_check(c, entry, p, nres, max_pods_per_node, scored_entry);
-  if (rc != MSH_OK) return rc;
-  if (p == 0) return MSH_OK;
-  DeviceGuard g(c->device);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const msh::SpreadArgs sa = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node,
-                                         d_out_idx, d_out_score, d_out_status);
-  // one sequential launch of a ctx at a time (seq_device): each commits into the same counts
-  for (auto& ev : c->seq_inflight)
-    if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
-  std::string err;
-  hipError_t e;
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;  // a _spread_scored call: spread_check let it pass
-  {
-    TimedLaunch tl(c);
-    if (scored) {  // the same argument block with the setting, as seq_device fills FitScoreArgs
-      msh::SpreadScoreArgs ssa{};
-      ssa.s = sa;
-      spread_score_setting(c, nres, ssa);
-      e = msh::launch_seq_spread_score(ssa, s, &err);
-    } else {
-      e = msh::launch_seq_spread(sa, s, &err);
-    }
-  }
-  if (e != hipSuccess) {
-    if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
-    return hip_fail(c, e, scored ? "seq_spread_score_kernel" : "seq_spread_kernel");
-  }
-  c->counts_dirty = false;  // the one workgroup folded the replicas
-  spread_bound_add(c, d_pod_group != nullptr, p);
-  return track_launch(c, s, true);
-}
-}  // namespace
-
-int msh_schedule_sequential_spread_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                                          const int32_t* d_pod_group, int32_t nres, const int64_t* d_pod_req,
-                                          int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
-                                          int32_t* d_out_status, void* stream) {
-  return spread_device(c, "msh_schedule_sequential_spread_device", p, d_pod_digit, d_pod_tol, d_pod_group, nres,
-                       d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, false);
-}
-
-int msh_schedule_sequential_spread_scored_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
-                                                 const uint8_t* d_pod_tol, const int32_t* d_pod_group, int32_t nres,
-                                                 const int64_t* d_pod_req, int32_t max_pods_per_node,
-                                                 int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
-                                                 void* stream) {
-  return spread_device(c, "msh_schedule_sequential_spread_scored_device", p, d_pod_digit, d_pod_tol, d_pod_group,
-                       nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, true);
-}
-
-namespace {
-// msh_schedule_sequential_spread and msh_schedule_sequential_spread_scored
-int spread_host(msh_ctx* c, const char* entry, bool scored_entry, int32_t p, const int8_t* pod_digit,
-                const uint8_t* pod_tol, const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
-                int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score, int32_t* out_status,
-                msh_commit_cb commit_cb, void* user) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (p > 0 && (!pod_digit || !pod_tol || !pod_group || !out_idx || !out_status))  // out_score optional
-    return fail(c, MSH_ERR_INVALID, "null host pointer");
-  if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
-  int rc = spread_check(c, entry, p, nres, max_pods_per_node, scored_entry);
-  if (rc != MSH_OK) return rc;
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  for (int32_t j = 0; j < p; ++j)
-    if (pod_group[j] < -1 || pod_group[j] >= c->sp_groups)
-      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": group " + std::to_string(pod_group[j]) +
-                                          " outside [-1, G) with G = " + std::to_string(c->sp_groups));
-  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
-    if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
-      return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
-    if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
-      return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
-                                          std::to_string(e % (size_t)p));
-  }
-  if (p == 0) return MSH_OK;
-  DeviceGuard g(c->device);
-  HostIO io;
-  if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  // the requests and the groups through the page-locked node stage, which the kernel reads itself (free here:
-  // every writer that uses it has finished its copies, and this call ends only when the kernel has)
-  const size_t rbytes = (size_t)nres * (size_t)p * sizeof(int64_t);
-  if ((rc = node_stage(c, rbytes + (size_t)p * sizeof(int32_t))) != MSH_OK) return rc;
-  if (rbytes) std::memcpy(c->h_nstage, pod_req, rbytes);
-  std::memcpy(c->h_nstage + rbytes, pod_group, (size_t)p * sizeof(int32_t));
-  rc = spread_device(c, entry, p, io.d_pd, io.d_pt, reinterpret_cast<const int32_t*>(c->h_nstage + rbytes), nres,
-                     reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
-                     io.o_status, c->stream, scored_entry);
-  if (rc != MSH_OK) return rc;
-  if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  if (commit_cb)
-    for (int32_t j = 0; j < p; j++)
-      if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
-  return MSH_OK;
-}
-}  // namespace
-
-int msh_schedule_sequential_spread(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                   const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
-                                   int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
-                                   int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  return spread_host(c, "msh_schedule_sequential_spread", false, p, pod_digit, pod_tol, pod_group, nres, pod_req,
-                     max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
-}
-
-int msh_schedule_sequential_spread_scored(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                          const int32_t* pod_group, int32_t nres, const int64_t* pod_req,
-                                          int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
-                                          int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  return spread_host(c, "msh_schedule_sequential_spread_scored", true, p, pod_digit, pod_tol, pod_group, nres,
-                     pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
-}
-
-// The per-class node masks (msh_schedule_sequential_classes). The column is the capacity column's in lifetime and
-// ordering: unversioned, written through prep_stream behind the sequential launches in flight, which read it at
-// their start, and each writer finishes before it returns.
-namespace {
-// a device column of n_pad words; a larger one is allocated before the old one is let go, so a failure changes nothing
-int class_reserve(msh_ctx* c) {
-  if ((size_t)c->n_pad <= c->class_cap) return MSH_OK;
-  uint64_t* d = nullptr;
-  MSH_HIP(c, hipMalloc(&d, (size_t)c->n_pad * sizeof(uint64_t)));
-  wait_events(c->seq_inflight);
-  (void)hipFree(c->d_class);
-  c->d_class = d;
-  c->class_cap = (size_t)c->n_pad;
-  c->have_class = false;  // the old column went with its buffer
-  c->pref_dirty = true;
-  c->h_class.clear();
-  c->n_classes = 0;
-  return MSH_OK;
-}
-
-// the whole column from `bits` (n_nodes words; the padding slots 0: they never hold a node)
-int class_write_all(msh_ctx* c, const uint64_t* bits) {
-  const size_t bytes = (size_t)c->n_nodes * sizeof(uint64_t);
-  int rc = node_stage(c, bytes);
-  if (rc != MSH_OK) return rc;
-  if ((rc = after_seq(c)) != MSH_OK) return rc;
-  MSH_HIP(c, hipMemsetAsync(c->d_class, 0, c->class_cap * sizeof(uint64_t), c->prep_stream));
-  if (bytes > 0) {
-    std::memcpy(c->h_nstage, bits, bytes);
-    MSH_HIP(c, hipMemcpyAsync(c->d_class, c->h_nstage, bytes, hipMemcpyHostToDevice, c->prep_stream));
-  }
-  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
-  return MSH_OK;
-}
-
-bool class_bits_above(uint64_t w, int32_t C) { return C < MSH_MAX_POD_CLASSES && (w >> C) != 0; }
-}  // namespace
-
-int msh_upload_node_class_bits(msh_ctx* c, int32_t n, int32_t C, const uint64_t* bits) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (n != c->n_nodes)
-    return fail(c, MSH_ERR_INVALID, "class column of " + std::to_string(n) + " entries for " +
-                                        std::to_string(c->n_nodes) + " uploaded nodes");
-  if (C < 1 || C > MSH_MAX_POD_CLASSES) return fail(c, MSH_ERR_INVALID, "C outside [1, MSH_MAX_POD_CLASSES]");
-  if (n > 0 && !bits) return fail(c, MSH_ERR_INVALID, "null class bits array");
-  for (int32_t i = 0; i < n; ++i)
-    if (class_bits_above(bits[i], C))
-      return fail(c, MSH_ERR_INVALID, "a bit at or above C = " + std::to_string(C) + " is set at node " + std::to_string(i));
-  DeviceGuard g(c->device);
-  int rc = class_reserve(c);
-  if (rc != MSH_OK) return rc;
-  std::vector<uint64_t> h(bits, bits + n);
-  c->have_class = false;  // a failed copy leaves no column
-  c->pref_dirty = true;   // the preference table holds the masks' verdicts
-  if ((rc = class_write_all(c, h.data())) != MSH_OK) return rc;
-  c->h_class.swap(h);
-  c->n_classes = C;
-  c->have_class = true;
-  return MSH_OK;
-}
-
-int msh_patch_node_class_bits(msh_ctx* c, int32_t count, const int32_t* idx, const uint64_t* bits) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (!c->have_class) return fail(c, MSH_ERR_STATE, "msh_upload_node_class_bits has not been called");
-  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
-  if (count == 0) return MSH_OK;
-  if (!idx || !bits) return fail(c, MSH_ERR_INVALID, "null patch arrays");
-  std::vector<int32_t> sorted(idx, idx + count);
-  std::sort(sorted.begin(), sorted.end());
-  if (sorted.front() < 0 || sorted.back() >= c->n_nodes)
-    return fail(c, MSH_ERR_INVALID, "patch index outside [0, n)");
-  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-    return fail(c, MSH_ERR_INVALID, "duplicate patch index");
-  for (int32_t k = 0; k < count; ++k)
-    if (class_bits_above(bits[k], c->n_classes))
-      return fail(c, MSH_ERR_INVALID, "a bit at or above C = " + std::to_string(c->n_classes) +
-                                          " is set at patch entry " + std::to_string(k));
-  DeviceGuard g(c->device);
-  // the patched column whole: 64 KB at the largest table a class call takes, one copy
-  std::vector<uint64_t> h(c->h_class);
-  for (int32_t k = 0; k < count; ++k) h[(size_t)idx[k]] = bits[k];
-  c->pref_dirty = true;
-  int rc = class_write_all(c, h.data());
-  if (rc != MSH_OK) {
-    c->have_class = false;  // the device column is in an unknown state
-    return rc;
-  }
-  c->h_class.swap(h);
-  return MSH_OK;
-}
-
-int msh_clear_node_class_bits(msh_ctx* c) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  c->have_class = false;  // launches in flight keep reading the device column, which stays allocated
-  c->pref_dirty = true;
-  c->h_class.clear();
-  c->n_classes = 0;
-  return MSH_OK;
-}
-
-int msh_node_class_bits(msh_ctx* c, int32_t* out_C, uint64_t* out_bits, int32_t* out_present) {
-  if (!c || !out_present) return MSH_ERR_INVALID;
-  c->err.clear();
-  *out_present = c->have_class ? 1 : 0;
-  if (out_C) *out_C = c->have_class ? c->n_classes : 0;
-  if (c->have_class && out_bits) std::copy(c->h_class.begin(), c->h_class.end(), out_bits);
-  return MSH_OK;
-}
-
-int msh_seq_classes_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
-  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
-  *out_max_nodes = msh::seq_classes_max_nodes(nres, c->rs_mode != MSH_RESOURCE_SCORE_NONE);
-  return MSH_OK;
-}
-
-namespace {
-// What a classes call needs, checked before any device work: _spread_scored's refusals in its order, with the zone
-// column required only when the call has groups, the class column only when it has classes, and the class
-// kernels' table limits.
-int classes_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node, bool grouped,
-                  bool classed) {
-  if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
-  if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
-  int rc = refuse_soft_groups(c, entry, grouped);
-  if (rc != MSH_OK) return rc;
-  if ((rc = refuse_random(c, entry)) != MSH_OK) return rc;
-  if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (grouped && !c->have_zone) return fail(c, MSH_ERR_STATE, "msh_upload_node_zones has not been called");
-  if (classed && !c->have_class) return fail(c, MSH_ERR_STATE, "msh_upload_node_class_bits has not been called");
-  if (nres) {
-    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
-    if (nres != c->nres)
-      return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
-                                          std::to_string(c->nres));
-  }
-  if (scored) {
-    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
-    if (nres != c->rs_nres)
-      return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
-                                        " resources, the call has " + std::to_string(nres));
-  }
-  const int32_t lim = msh::seq_classes_max_nodes(nres, scored);
-  if (c->n_nodes > lim)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                msh::seq_table_limit_message(scored ? "scored class-mask" : "class-mask", lim, nres));
-  if (scored && c->res_max > MSH_RESOURCE_SCORE_MAX)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
-                "or patch wrote " + std::to_string(c->res_max));
-  return MSH_OK;
-}
-
-int classes_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                   const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
-                   int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
-                   void* stream) {
-  if (!c) return MSH_ERR_INVALID;
-  // no classes in the call: _spread_scored itself, the same kernel instance
-  if (!d_pod_class && d_pod_group)
-    return spread_device(c, entry, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
-                         d_out_score, d_out_status, stream, true);
-  c->err.clear();
-  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // group, class and score optional
-    return fail(c, MSH_ERR_INVALID, "null device pointer");
-  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = classes_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr);
-  if (rc != MSH_OK) return rc;
-  if (p == 0) return MSH_OK;
-  DeviceGuard g(c->device);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  msh::ClassArgs ca{};
-  ca.ss.s = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
-                        d_out_score, d_out_status);
-  if (scored) spread_score_setting(c, nres, ca.ss);
-  ca.class_bits = d_pod_class ? c->d_class : nullptr;
-  ca.pod_class = d_pod_class;
-  ca.n_classes = d_pod_class ? c->n_classes : 0;
-  // one sequential launch of a ctx at a time (seq_device): each commits into the same counts
-  for (auto& ev : c->seq_inflight)
-    if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
-  std::string err;
-  hipError_t e;
-  {
-    TimedLaunch tl(c);
-    e = msh::launch_seq_classes(ca, scored, s, &err);
-  }
-  if (e != hipSuccess) {
-    if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
-    return hip_fail(c, e, scored ? "seq_classes_score_kernel" : "seq_classes_kernel");
-  }
-  c->counts_dirty = false;  // the one workgroup folded the replicas
-  spread_bound_add(c, d_pod_group != nullptr, p);
-  return track_launch(c, s, true);
-}
-}  // namespace
-
-int msh_schedule_sequential_classes_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                                           const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
-                                           const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
-                                           int64_t* d_out_score, int32_t* d_out_status, void* stream) {
-  return classes_device(c, "msh_schedule_sequential_classes_device", p, d_pod_digit, d_pod_tol, d_pod_group,
-                        d_pod_class, nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
-}
-
-int msh_schedule_sequential_classes(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                    const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
-                                    const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
-                                    int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  const char* entry = "msh_schedule_sequential_classes";
-  if (!c) return MSH_ERR_INVALID;
-  if (!pod_class && pod_group)  // no classes in the call: _spread_scored itself
-    return spread_host(c, entry, true, p, pod_digit, pod_tol, pod_group, nres, pod_req, max_pods_per_node, out_idx,
-                       out_score, out_status, commit_cb, user);
-  c->err.clear();
-  if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // group, class and score optional
-    return fail(c, MSH_ERR_INVALID, "null host pointer");
-  if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
-  int rc = classes_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr);
-  if (rc != MSH_OK) return rc;
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  for (int32_t j = 0; pod_group && j < p; ++j)
-    if (pod_group[j] < -1 || pod_group[j] >= c->sp_groups)
-      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": group " + std::to_string(pod_group[j]) +
-                                          " outside [-1, G) with G = " + std::to_string(c->sp_groups));
-  for (int32_t j = 0; pod_class && j < p; ++j)
-    if (pod_class[j] < -1 || pod_class[j] >= c->n_classes)
-      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": class " + std::to_string(pod_class[j]) +
-                                          " outside [-1, C) with C = " + std::to_string(c->n_classes));
-  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
-    if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
-      return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
-    if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
-      return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
-                                          std::to_string(e % (size_t)p));
-  }
-  if (p == 0) return MSH_OK;
-  DeviceGuard g(c->device);
-  HostIO io;
-  if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  // the requests, groups and classes through the page-locked node stage, which the kernel reads itself (spread_host)
-  const size_t rbytes = (size_t)nres * (size_t)p * sizeof(int64_t), cbytes = (size_t)p * sizeof(int32_t);
-  if ((rc = node_stage(c, rbytes + 2 * cbytes)) != MSH_OK) return rc;
-  if (rbytes) std::memcpy(c->h_nstage, pod_req, rbytes);
-  int32_t* sg = reinterpret_cast<int32_t*>(c->h_nstage + rbytes);
-  int32_t* sc = reinterpret_cast<int32_t*>(c->h_nstage + rbytes + cbytes);
-  if (pod_group) std::memcpy(sg, pod_group, cbytes);
-  if (pod_class) std::memcpy(sc, pod_class, cbytes);
-  rc = classes_device(c, entry, p, io.d_pd, io.d_pt, pod_group ? sg : nullptr, pod_class ? sc : nullptr, nres,
-                      reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
-                      io.o_status, c->stream);
-  if (rc != MSH_OK) return rc;
-  if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  if (commit_cb)
-    for (int32_t j = 0; j < p; j++)
-      if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
-  return MSH_OK;
-}
-
-// The per-class preference values (msh_schedule_sequential_prefs). The host copies are the column; the device table
-// the kernel reads is derived from them and from the class masks by the first call after either changed
-// (prefs_table), so the writers touch no device memory and cannot leave the device in an unknown state.
-namespace {
-void prefs_drop(msh_ctx* c) {
-  c->have_prefs = false;
-  c->pref_classes = 0;
-  c->h_pref_a.clear();
-  c->h_pref_t.clear();
-  c->pref_dirty = true;
-}
-
-// The device table for the ctx's columns and a kernel of npl nodes per thread (msh::PrefArgs::rows): classes x
-// PREF_THREADS records of 2 * npl dwords. Ordered after the sequential launches in flight, which read the old one
-// until they end; synchronous.
-int prefs_table(msh_ctx* c, int32_t npl) {
-  const int32_t C = c->have_prefs ? c->pref_classes : (c->have_class ? c->n_classes : 0);
-  if (!c->pref_dirty && c->pref_dev_classes == C && c->pref_stride == 2 * npl) return MSH_OK;
-  const size_t rec = 2 * (size_t)npl, per_class = rec * msh::PREF_THREADS, total = per_class * (size_t)C;
-  std::vector<uint32_t> h(total, 0u);
-  uint64_t am = 0, tm = 0;
-  const size_t n = (size_t)c->n_nodes;
-  for (int32_t k = 0; k < C; ++k) {
-    uint32_t* row = h.data() + per_class * (size_t)k;
-    for (size_t i = 0; i < n; ++i) {
-      const uint32_t av = c->have_prefs && !c->h_pref_a.empty() ? c->h_pref_a[(size_t)k * n + i] : 0u;
-      const uint32_t tv = c->have_prefs && !c->h_pref_t.empty() ? c->h_pref_t[(size_t)k * n + i] : 0u;
-      const bool admits = !c->have_class || ((c->h_class[i] >> k) & 1ull) != 0;
-      uint32_t* r = row + (i / (size_t)npl) * rec;
-      r[i % (size_t)npl] = av | (tv << 16);
-      r[npl] |= (admits ? 1u : 0u) << (i % (size_t)npl);
-      if (av) am |= 1ull << k;
-      if (tv) tm |= 1ull << k;
-    }
-  }
-  wait_events(c->seq_inflight);
-  if (total > c->pref_cap) {
-    uint32_t* d = nullptr;
-    MSH_HIP(c, hipMalloc(&d, total * sizeof(uint32_t)));
-    (void)hipFree(c->d_pref);
-    c->d_pref = d;
-    c->pref_cap = total;
-    c->pref_dirty = true;  // the old table went with its buffer
-  }
-  if (total) MSH_HIP(c, hipMemcpy(c->d_pref, h.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice));
-  c->pref_dev_classes = C;
-  c->pref_stride = 2 * npl;
-  c->pref_amask = am;
-  c->pref_tmask = tm;
-  c->pref_dirty = false;
-  return MSH_OK;
-}
-}  // namespace
-
-int msh_upload_node_class_prefs(msh_ctx* c, int32_t n, int32_t C, const uint16_t* affinity, const uint16_t* taints) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (n != c->n_nodes)
-    return fail(c, MSH_ERR_INVALID, "preference column of " + std::to_string(n) + " entries per class for " +
-                                        std::to_string(c->n_nodes) + " uploaded nodes");
-  if (C < 1 || C > MSH_MAX_POD_CLASSES) return fail(c, MSH_ERR_INVALID, "C outside [1, MSH_MAX_POD_CLASSES]");
-  const size_t len = (size_t)C * (size_t)n;
-  std::vector<uint16_t> a, t;  // an absent array stays empty: all zero
-  if (affinity) a.assign(affinity, affinity + len);
-  if (taints) t.assign(taints, taints + len);
-  c->h_pref_a.swap(a);
-  c->h_pref_t.swap(t);
-  c->pref_classes = C;
-  c->have_prefs = true;
-  c->pref_dirty = true;
-  return MSH_OK;
-}
-
-int msh_patch_node_class_prefs(msh_ctx* c, int32_t count, const int32_t* idx, const uint16_t* affinity,
-                               const uint16_t* taints) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (!c->have_prefs) return fail(c, MSH_ERR_STATE, "msh_upload_node_class_prefs has not been called");
-  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
-  if (count == 0) return MSH_OK;
-  if (!idx) return fail(c, MSH_ERR_INVALID, "null patch indices");
-  std::vector<int32_t> sorted(idx, idx + count);
-  std::sort(sorted.begin(), sorted.end());
-  if (sorted.front() < 0 || sorted.back() >= c->n_nodes)
-    return fail(c, MSH_ERR_INVALID, "patch index outside [0, n)");
-  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-    return fail(c, MSH_ERR_INVALID, "duplicate patch index");
-  const size_t n = (size_t)c->n_nodes, C = (size_t)c->pref_classes;
-  auto apply = [&](std::vector<uint16_t>& col, const uint16_t* v) {  // a null array writes zeros
-    if (col.empty() && !v) return;
-    if (col.empty()) col.assign(C * n, 0);
-    for (size_t k = 0; k < C; ++k)
-      for (int32_t e = 0; e < count; ++e) col[k * n + (size_t)idx[e]] = v ? v[k * (size_t)count + (size_t)e] : 0;
-  };
-  apply(c->h_pref_a, affinity);
-  apply(c->h_pref_t, taints);
-  c->pref_dirty = true;
-  return MSH_OK;
-}
-
-int msh_clear_node_class_prefs(msh_ctx* c) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  prefs_drop(c);  // launches in flight keep reading the device table, which stays allocated
-  return MSH_OK;
-}
-
-int msh_node_class_prefs(msh_ctx* c, int32_t* out_C, uint16_t* out_affinity, uint16_t* out_taints,
-                         int32_t* out_present) {
-  if (!c || !out_present) return MSH_ERR_INVALID;
-  c->err.clear();
-  *out_present = c->have_prefs ? 1 : 0;
-  if (out_C) *out_C = c->have_prefs ? c->pref_classes : 0;
-  if (!c->have_prefs) return MSH_OK;
-  const size_t len = (size_t)c->pref_classes * (size_t)c->n_nodes;
-  auto give = [&](const std::vector<uint16_t>& col, uint16_t* out) {
-    if (!out) return;
-    if (col.empty()) std::fill(out, out + len, (uint16_t)0);
-    else std::copy(col.begin(), col.end(), out);
-  };
-  give(c->h_pref_a, out_affinity);
-  give(c->h_pref_t, out_taints);
-  return MSH_OK;
-}
-
-int msh_set_preference_weights(msh_ctx* c, int32_t w_affinity, int32_t w_taint) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (w_affinity < 0 || w_affinity > 100 || w_taint < 0 || w_taint > 100)
-    return fail(c, MSH_ERR_INVALID, "preference weight outside [0, 100]");
-  c->w_aff = w_affinity;
-  c->w_taint = w_taint;
-  return MSH_OK;
-}
-
-int msh_preference_weights(const msh_ctx* c, int32_t* out_w_affinity, int32_t* out_w_taint) {
-  if (!c) return MSH_ERR_INVALID;
-  if (out_w_affinity) *out_w_affinity = c->w_aff;
-  if (out_w_taint) *out_w_taint = c->w_taint;
-  return MSH_OK;
-}
-
-int msh_seq_prefs_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
-  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
-  *out_max_nodes = msh::seq_prefs_max_nodes(nres);
-  return MSH_OK;
-}
-
-namespace {
-// the classes of a prefs call: the columns' common C (0 without a column)
-int32_t prefs_classes(const msh_ctx* c) { return c->have_prefs ? c->pref_classes : (c->have_class ? c->n_classes : 0); }
-
-// What a prefs call with a nonzero weight needs, checked before any device work: _classes's refusals in its order
-// (the class column is not required by itself), with the preference kernel's table limits, then the two of this
-// call: pod classes with neither column (and columns of unequal C), and a weighted sum the packed key cannot hold.
-int prefs_check(msh_ctx* c, const char* entry, int32_t p, int32_t nres, int32_t max_pods_per_node, bool grouped,
-                bool classed, bool soft_entry = false, bool balanced = false) {
-  if (p < 0 || max_pods_per_node < 0) return fail(c, MSH_ERR_INVALID, "negative argument");
-  if (nres < 0 || nres > MSH_MAX_RESOURCES) return fail(c, MSH_ERR_INVALID, "nres outside [0, MSH_MAX_RESOURCES]");
-  int rc = soft_entry ? MSH_OK : refuse_soft_groups(c, entry, grouped);
-  if (rc != MSH_OK) return rc;
-  if ((rc = refuse_random(c, entry)) != MSH_OK) return rc;
-  if (c->generic) return fail(c, MSH_ERR_UNSUPPORTED, "score-column plugins run on the batch entry points only");
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
-  if (grouped && !c->have_zone) return fail(c, MSH_ERR_STATE, "msh_upload_node_zones has not been called");
-  if (balanced) {  // the balanced score reads the table's first two resources in every resource score mode
-    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
-    if (c->nres < 2)
-      return fail(c, MSH_ERR_STATE, "the balanced score needs a resource table with at least two resources, the "
-                                    "table has " + std::to_string(c->nres));
-    if (nres != c->nres)
-      return fail(c, MSH_ERR_STATE, "the balanced score needs the requests of all " + std::to_string(c->nres) +
-                                        " resources of the table, the call has " + std::to_string(nres));
-  }
-  if (nres) {
-    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
-    if (nres != c->nres)
-      return fail(c, MSH_ERR_INVALID, "requests for " + std::to_string(nres) + " resources against a table of " +
-                                          std::to_string(c->nres));
-  }
-  if (scored) {
-    if (!c->have_res) return fail(c, MSH_ERR_STATE, "msh_upload_node_resources has not been called");
-    if (nres != c->rs_nres)
-      return fail(c, MSH_ERR_STATE, "msh_set_resource_score was given " + std::to_string(c->rs_nres) +
-                                        " resources, the call has " + std::to_string(nres));
-  }
-  const int32_t lim = balanced ? msh::seq_balanced_max_nodes(nres)
-                               : (soft_entry ? msh::seq_soft_max_nodes(nres) : msh::seq_prefs_max_nodes(nres));
-  if (c->n_nodes > lim)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                msh::seq_table_limit_message(balanced ? "balanced-allocation" : (soft_entry ? "soft-spread" : "preference"),
-                                             lim, nres));
-  if (scored && c->res_max > MSH_RESOURCE_SCORE_MAX)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                "a resource score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
-                "or patch wrote " + std::to_string(c->res_max));
-  if (balanced && c->res_max > MSH_RESOURCE_SCORE_MAX)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                "the balanced score needs every amount of the table within MSH_RESOURCE_SCORE_MAX = 2^55; an upload "
-                "or patch wrote " + std::to_string(c->res_max));
-  if (classed && !c->have_class && !c->have_prefs)
-    return fail(c, MSH_ERR_STATE, "pod classes with neither msh_upload_node_class_prefs nor msh_upload_node_class_bits");
-  if (classed && c->have_class && c->have_prefs && c->n_classes != c->pref_classes)
-    return fail(c, MSH_ERR_STATE, "the class masks were uploaded for C = " + std::to_string(c->n_classes) +
-                                      ", the preference values for C = " + std::to_string(c->pref_classes));
-  const int64_t wsum = (scored ? c->rs_weight : 0) + c->w_aff + c->w_taint;
-  if (100 * wsum > 65534)
-    return fail(c, MSH_ERR_UNSUPPORTED, "the weights of the resource score and the two preference scores sum to " +
-                                            std::to_string(wsum) + ": the packed key holds 100 x 655 at most");
-  if (!soft_entry) return MSH_OK;
-  // msh_schedule_sequential_soft's own two, after the others: the key with the spread weight, and the counts' bound
-  if (100 * (wsum + c->w_spread) > 65534)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                "the weights of the resource score, the two preference scores and the spread score sum to " +
-                    std::to_string(wsum + c->w_spread) + ": the packed key holds 100 x 655 at most");
-  if (balanced && 100 * (wsum + c->w_spread + c->w_balanced) > 65534)
-    return fail(c, MSH_ERR_UNSUPPORTED,
-                "the weights of the resource score, the two preference scores, the spread score and the balanced score "
-                "sum to " + std::to_string(wsum + c->w_spread + c->w_balanced) + ": the packed key holds 100 x 655 at most");
-  // the counts' bounds belong to the soft groups' term: a balanced call on a ctx without one runs none of it
-  if (grouped && (!balanced || c->sp_soft > 0)) {
-    if (c->sp_cnt_bound > MSH_SPREAD_SOFT_MAX)
-      return fail(c, MSH_ERR_UNSUPPORTED, "a spread count may have reached " + std::to_string(c->sp_cnt_bound) +
-                                              ", above MSH_SPREAD_SOFT_MAX = 2^24 (msh_reset_spread_counts zeroes them)");
-    if (p > MSH_SPREAD_SOFT_MAX)
-      return fail(c, MSH_ERR_UNSUPPORTED, "a soft-spread call takes at most MSH_SPREAD_SOFT_MAX = 2^24 pods");
-    for (int32_t g = 0; g < c->sp_groups; ++g)
-      if (c->h_spmode[(size_t)g] == MSH_SPREAD_SCHEDULE_ANYWAY && c->h_skew[(size_t)g] > MSH_SPREAD_SOFT_MAX)
-        return fail(c, MSH_ERR_UNSUPPORTED, "SCHEDULE_ANYWAY group " + std::to_string(g) + " has max_skew " +
-                                                std::to_string(c->h_skew[(size_t)g]) +
-                                                ", above MSH_SPREAD_SOFT_MAX = 2^24");
-  }
-  return MSH_OK;
-}
-
-// the weights log(size + 2) on the device, uploaded once (synchronous)
-int soft_weights_device(msh_ctx* c) {
-  if (c->d_zone_weight) return MSH_OK;
-  double* d = nullptr;
-  const size_t bytes = (size_t)(MSH_MAX_ZONES + 1) * sizeof(double);
-  MSH_HIP(c, hipMalloc(&d, bytes));
-  const hipError_t e = hipMemcpy(d, soft_weights(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d);
-    return hip_fail(c, e, "spread score weights");
-  }
-  c->d_zone_weight = d;
-  return MSH_OK;
-}
-
-// soft: msh_schedule_sequential_soft on a ctx with a SCHEDULE_ANYWAY group (seq_soft_kernel); else the preference call
-int prefs_device(msh_ctx* c, const char* entry, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                 const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres, const int64_t* d_pod_req,
-                 int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
-                 void* stream, bool soft = false, bool balanced = false) {
-  c->err.clear();
-  if (p > 0 && (!d_pod_digit || !d_pod_tol || !d_out_idx || !d_out_status))  // group, class and score optional
-    return fail(c, MSH_ERR_INVALID, "null device pointer");
-  if (nres > 0 && p > 0 && !d_pod_req) return fail(c, MSH_ERR_INVALID, "null device pointer");
-  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, d_pod_group != nullptr, d_pod_class != nullptr, soft,
-                       balanced);
-  if (rc != MSH_OK) return rc;
-  if (p == 0) return MSH_OK;
-  DeviceGuard g(c->device);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  static_assert(msh::SPREAD_SOFT_MAX == MSH_SPREAD_SOFT_MAX, "the kernel's bound is the header's");
-  const int32_t npl = balanced ? msh::seq_balanced_npl(nres) : (soft ? msh::seq_soft_npl(nres) : msh::seq_prefs_npl(nres));
-  if (d_pod_class && (rc = prefs_table(c, npl)) != MSH_OK) return rc;
-  if (soft && (!balanced || c->sp_soft > 0) && (rc = soft_weights_device(c)) != MSH_OK) return rc;
-  msh::BalancedArgs ba{};
-  msh::SoftArgs& so = ba.so;
-  msh::PrefArgs& pa = so.p;
-  pa.ss.s = spread_args(c, p, d_pod_digit, d_pod_tol, d_pod_group, nres, d_pod_req, max_pods_per_node, d_out_idx,
-                        d_out_score, d_out_status);
-  if (scored) spread_score_setting(c, nres, pa.ss);  // else weight 0, every resource weight 0 and the magic 0: rs = 0
-  pa.rows = d_pod_class ? c->d_pref : nullptr;
-  pa.pod_class = d_pod_class;
-  pa.n_classes = d_pod_class ? c->pref_dev_classes : 0;
-  pa.amask = d_pod_class ? c->pref_amask : 0;
-  pa.tmask = d_pod_class ? c->pref_tmask : 0;
-  pa.w_aff = (uint32_t)c->w_aff;
-  pa.w_taint = (uint32_t)c->w_taint;
-  // one sequential launch of a ctx at a time (seq_device): each commits into the same counts
-  for (auto& ev : c->seq_inflight)
-    if (ev.first != s) MSH_HIP(c, hipStreamWaitEvent(s, ev.second, 0));
-  std::string err;
-  hipError_t e;
-  {
-    TimedLaunch tl(c);
-    if (soft) {
-      for (int32_t k = 0; d_pod_group && k < c->sp_groups; ++k)
-        if (c->h_spmode[(size_t)k] == MSH_SPREAD_SCHEDULE_ANYWAY) so.soft[k >> 6] |= uint64_t(1) << (k & 63);
-      so.w_spread = (uint32_t)c->w_spread;
-      so.zone_weight = c->d_zone_weight;
-      ba.w_balanced = (uint32_t)c->w_balanced;
-      e = balanced ? msh::launch_seq_balanced(ba, s, &err) : msh::launch_seq_soft(so, s, &err);
-    } else {
-      e = msh::launch_seq_prefs(pa, s, &err);
-    }
-  }
-  if (e != hipSuccess) {
-    if (!err.empty()) return fail(c, MSH_ERR_UNSUPPORTED, err);
-    return hip_fail(c, e, balanced ? "seq_balanced_kernel" : (soft ? "seq_soft_kernel" : "seq_prefs_kernel"));
-  }
-  c->counts_dirty = false;  // the one workgroup folded the replicas
-  spread_bound_add(c, d_pod_group != nullptr, p);
-  return track_launch(c, s, true);
-}
-}  // namespace
-
-int msh_schedule_sequential_prefs_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                                         const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
-                                         const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
-                                         int64_t* d_out_score, int32_t* d_out_status, void* stream) {
-  if (!c) return MSH_ERR_INVALID;
-  if (c->w_aff == 0 && c->w_taint == 0)  // nothing to add: _classes itself, its kernel instance
-    return classes_device(c, "msh_schedule_sequential_prefs_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
-                          nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
-  return prefs_device(c, "msh_schedule_sequential_prefs_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
-                      nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
-}
-
-namespace {
-// msh_schedule_sequential_prefs with a nonzero preference weight, and msh_schedule_sequential_soft on a ctx with a
-// SCHEDULE_ANYWAY group (soft), and msh_schedule_sequential_balanced with a nonzero weight (soft and balanced)
-int prefs_host(msh_ctx* c, const char* entry, bool soft, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-               const int32_t* pod_group, const int32_t* pod_class, int32_t nres, const int64_t* pod_req,
-               int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score, int32_t* out_status,
-               msh_commit_cb commit_cb, void* user, bool balanced = false) {
-  c->err.clear();
-  if (p > 0 && (!pod_digit || !pod_tol || !out_idx || !out_status))  // group, class and score optional
-    return fail(c, MSH_ERR_INVALID, "null host pointer");
-  if (nres > 0 && p > 0 && !pod_req) return fail(c, MSH_ERR_INVALID, "null host pointer");
-  int rc = prefs_check(c, entry, p, nres, max_pods_per_node, pod_group != nullptr, pod_class != nullptr, soft, balanced);
-  if (rc != MSH_OK) return rc;
-  const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;
-  const int32_t C = prefs_classes(c);
-  for (int32_t j = 0; pod_group && j < p; ++j)
-    if (pod_group[j] < -1 || pod_group[j] >= c->sp_groups)
-      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": group " + std::to_string(pod_group[j]) +
-                                          " outside [-1, G) with G = " + std::to_string(c->sp_groups));
-  for (int32_t j = 0; pod_class && j < p; ++j)
-    if (pod_class[j] < -1 || pod_class[j] >= C)
-      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": class " + std::to_string(pod_class[j]) +
-                                          " outside [-1, C) with C = " + std::to_string(C));
-  for (size_t e = 0; e < (size_t)nres * (size_t)p; ++e) {
-    if (pod_req[e] < 0 || pod_req[e] > MSH_RESOURCE_MAX)
-      return fail(c, MSH_ERR_INVALID, "request outside [0, 2^62] at pod " + std::to_string(e % (size_t)p));
-    if (scored && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
-      return fail(c, MSH_ERR_INVALID, "a resource score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
-                                          std::to_string(e % (size_t)p));
-    if (balanced && pod_req[e] > MSH_RESOURCE_SCORE_MAX)
-      return fail(c, MSH_ERR_INVALID, "the balanced score needs every request within MSH_RESOURCE_SCORE_MAX = 2^55: pod " +
-                                          std::to_string(e % (size_t)p));
-  }
-  if (p == 0) return MSH_OK;
-  DeviceGuard g(c->device);
-  HostIO io;
-  if ((rc = host_io_begin(c, p, pod_digit, pod_tol, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  // the requests, groups and classes through the page-locked node stage, which the kernel reads itself (spread_host)
-  const size_t rbytes = (size_t)nres * (size_t)p * sizeof(int64_t), cbytes = (size_t)p * sizeof(int32_t);
-  if ((rc = node_stage(c, rbytes + 2 * cbytes)) != MSH_OK) return rc;
-  if (rbytes) std::memcpy(c->h_nstage, pod_req, rbytes);
-  int32_t* sg = reinterpret_cast<int32_t*>(c->h_nstage + rbytes);
-  int32_t* sc = reinterpret_cast<int32_t*>(c->h_nstage + rbytes + cbytes);
-  if (pod_group) std::memcpy(sg, pod_group, cbytes);
-  if (pod_class) std::memcpy(sc, pod_class, cbytes);
-  rc = prefs_device(c, entry, p, io.d_pd, io.d_pt, pod_group ? sg : nullptr, pod_class ? sc : nullptr, nres,
-                    reinterpret_cast<const int64_t*>(c->h_nstage), max_pods_per_node, io.o_idx, io.o_score,
-                    io.o_status, c->stream, soft, balanced);
-  if (rc != MSH_OK) return rc;
-  if ((rc = host_io_end(c, p, out_idx, out_score, out_status, io)) != MSH_OK) return rc;
-  if (commit_cb)
-    for (int32_t j = 0; j < p; j++)
-      if (out_status[j] == MSH_PLACED) commit_cb(user, j, out_idx[j], out_score ? out_score[j] : 0);
-  return MSH_OK;
-}
-}  // namespace
-
-int msh_schedule_sequential_prefs(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                  const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
-                                  const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
-                                  int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  if (!c) return MSH_ERR_INVALID;
-  if (c->w_aff == 0 && c->w_taint == 0)  // nothing to add: _classes itself
-    return msh_schedule_sequential_classes(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
-                                           max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
-  return prefs_host(c, "msh_schedule_sequential_prefs", false, p, pod_digit, pod_tol, pod_group, pod_class, nres,
-                    pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
-}
-
-// Soft topology spread. With no SCHEDULE_ANYWAY group on the ctx there is nothing to add to any pod: the call is
-// _prefs itself, its kernel instance, whatever the spread weight is.
-int msh_seq_soft_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
-  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
-  *out_max_nodes = msh::seq_soft_max_nodes(nres);
-  return MSH_OK;
-}
-
-int msh_schedule_sequential_soft_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                                        const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
-                                        const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
-                                        int64_t* d_out_score, int32_t* d_out_status, void* stream) {
-  if (!c) return MSH_ERR_INVALID;
-  if (c->sp_soft == 0)
-    return msh_schedule_sequential_prefs_device(c, p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class, nres, d_pod_req,
-                                                max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
-  return prefs_device(c, "msh_schedule_sequential_soft_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
-                      nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, true);
-}
-
-int msh_schedule_sequential_soft(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                 const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
-                                 const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
-                                 int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  if (!c) return MSH_ERR_INVALID;
-  if (c->sp_soft == 0)
-    return msh_schedule_sequential_prefs(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
-                                         max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
-  return prefs_host(c, "msh_schedule_sequential_soft", true, p, pod_digit, pod_tol, pod_group, pod_class, nres,
-                    pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
-}
-
-// NodeResourcesBalancedAllocation. With w_balanced == 0 there is nothing to add to any pod: the call is _soft itself.
-// With a nonzero weight every pod has the term, so the balanced kernel runs whatever the ctx's groups are.
-int msh_set_balanced_score(msh_ctx* c, int32_t w_balanced) {
-  if (!c) return MSH_ERR_INVALID;
-  c->err.clear();
-  if (w_balanced < 0 || w_balanced > 100) return fail(c, MSH_ERR_INVALID, "balanced score weight outside [0, 100]");
-  c->w_balanced = w_balanced;
-  return MSH_OK;
-}
-
-int msh_balanced_score(const msh_ctx* c, int32_t* out_w) {
-  if (!c) return MSH_ERR_INVALID;
-  if (out_w) *out_w = c->w_balanced;
-  return MSH_OK;
-}
-
-int msh_seq_balanced_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
-  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
-  *out_max_nodes = msh::seq_balanced_max_nodes(nres);
-  return MSH_OK;
-}
-
-int msh_schedule_sequential_balanced_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
-                                            const int32_t* d_pod_group, const int32_t* d_pod_class, int32_t nres,
-                                            const int64_t* d_pod_req, int32_t max_pods_per_node, int32_t* d_out_idx,
-                                            int64_t* d_out_score, int32_t* d_out_status, void* stream) {
-  if (!c) return MSH_ERR_INVALID;
-  if (c->w_balanced == 0)
-    return msh_schedule_sequential_soft_device(c, p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class, nres, d_pod_req,
-                                               max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream);
-  return prefs_device(c, "msh_schedule_sequential_balanced_device", p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class,
-                      nres, d_pod_req, max_pods_per_node, d_out_idx, d_out_score, d_out_status, stream, true, true);
-}
-
-int msh_schedule_sequential_balanced(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
-                                     const int32_t* pod_group, const int32_t* pod_class, int32_t nres,
-                                     const int64_t* pod_req, int32_t max_pods_per_node, int32_t* out_idx,
-                                     int64_t* out_score, int32_t* out_status, msh_commit_cb commit_cb, void* user) {
-  if (!c) return MSH_ERR_INVALID;
-  if (c->w_balanced == 0)
-    return msh_schedule_sequential_soft(c, p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req,
-                                        max_pods_per_node, out_idx, out_score, out_status, commit_cb, user);
-  return prefs_host(c, "msh_schedule_sequential_balanced", true, p, pod_digit, pod_tol, pod_group, pod_class, nres,
-                    pod_req, max_pods_per_node, out_idx, out_score, out_status, commit_cb, user, true);
 }
 
 int msh_keys_slot1_is_any(const msh_ctx* c, int32_t* out_flag) {

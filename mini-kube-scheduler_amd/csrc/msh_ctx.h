@@ -1,6 +1,7 @@
 // msh_ctx.h — the msh_ctx behind include/minisched_hip.h and the host helpers its translation units
-// share (msh_capi.cpp: single-device entry points; msh_shard.cpp: node-sharded merge, RCCL communicator
-// and device groups). Not part of the public ABI.
+// share (msh_capi.cpp: single-device entry points; msh_capi_seq.cpp: the grouped sequential-commit entry points
+// and the columns they read; msh_shard.cpp: node-sharded merge, RCCL communicator and device groups). Not part
+// of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -258,6 +259,40 @@ int host_io_end(msh_ctx* c, int32_t p, int32_t* out_idx, int64_t* out_score, int
 
 // Device-visible address of page-locked host memory (msh_host_alloc'd or registered), or nullptr.
 void* pinned_device_ptr(const void* p);
+
+// Host wait for the launches recorded in `evs` (their events are kept for reuse).
+void wait_events(const std::vector<std::pair<hipStream_t, hipEvent_t>>& evs);
+// Order prep_stream after the sequential launches in flight (device-side waits): they update the counts and
+// columns that a read, reset or re-upload touches next.
+int after_seq(msh_ctx* c);
+// The page-locked node staging buffer, at least `bytes` long (free on entry: every user finishes its copies).
+int node_stage(msh_ctx* c, size_t bytes);
+
+// What every sequential-commit call shares (seq_device / seq_host in msh_capi.cpp, the grouped forms in
+// msh_capi_seq.cpp).
+// The table, pod column, count, capacity and output fields of a.s for the ctx as it stands; max_pods and fold are
+// the caller's (the plain call's rules differ from the one-workgroup forms').
+void seq_args_fill(msh_ctx* c, msh::SeqArgs& a, int32_t p, const int8_t* d_pod_digit, const uint8_t* d_pod_tol,
+                   int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status);
+// The ctx's resource score setting (mode LEAST or MOST) for a scored launch with nres resources: A is
+// msh::FitScoreArgs or msh::SpreadScoreArgs, which carry the same four fields.
+template <class A>
+void resource_score_setting(const msh_ctx* c, int32_t nres, A& a) {
+  a.most = c->rs_mode == MSH_RESOURCE_SCORE_MOST_ALLOCATED ? 1 : 0;
+  a.weight = c->rs_weight;
+  uint32_t sum = 0;
+  for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(a.rw[r] = r < nres ? c->rs_w[r] : 0);
+  a.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
+}
+// The requests of a host call, [nres][p]: each within [0, 2^62]; with a resource score (scored), then with the
+// balanced score, within 2^55.
+int check_requests(msh_ctx* c, int32_t nres, int32_t p, const int64_t* pod_req, bool scored, bool balanced);
+// One sequential launch of a ctx at a time: each commits into (and a fold rewrites) the same counts, so stream s
+// first waits for the ctx's sequential launches in flight on other streams.
+int seq_serialize(msh_ctx* c, hipStream_t s);
+// The commit callback for every placed pod of a finished host call, in pod order.
+void commit_callbacks(msh_commit_cb cb, void* user, int32_t p, const int32_t* out_idx, const int64_t* out_score,
+                      const int32_t* out_status);
 
 }  // namespace msh::capi
 

@@ -492,14 +492,23 @@ class DeviceContext:
         group g is placed only on a node with a zone where cnt[g][zone] + 1 - min over the table's zones of cnt[g]
         stays within max_skew[g]; a placement adds 1 to cnt[g][zone]. pod_req (nres, p) as in
         schedule_sequential_fit, or None: no requests are checked or committed."""
-        return self._spread_host(self._lib.msh_schedule_sequential_spread, "schedule_sequential_spread", pod_digit,
-                                 pod_tol, pod_group, pod_req, max_pods_per_node, on_commit, out)
+        return self._grouped_host("schedule_sequential_spread", pod_digit, pod_tol, pod_group, None, pod_req,
+                                  max_pods_per_node, on_commit, out, classes=False)
 
-    def _spread_host(self, fn, name: str, pod_digit, pod_tol, pod_group, pod_req, max_pods_per_node, on_commit, out):
+    def _grouped_host(self, name: str, pod_digit, pod_tol, pod_group, pod_class, pod_req, max_pods_per_node, on_commit,
+                      out, classes: bool = True):
+        """msh_<name>, a host entry point of the grouped sequential calls. classes=False: a spread form, which has
+        no pod_class argument and requires pod_group."""
         pod_digit = np.ascontiguousarray(pod_digit, np.int8)
         pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
-        pod_group = self._int32s(pod_group, "pod_group")
-        p = _same_len(name, pod_digit, pod_tol, pod_group)
+        cols = [pod_digit, pod_tol]
+        if pod_group is not None or not classes:
+            pod_group = self._int32s(pod_group, "pod_group")
+            cols.append(pod_group)
+        if pod_class is not None:
+            pod_class = self._int32s(pod_class, "pod_class")
+            cols.append(pod_class)
+        p = _same_len(name, *cols)
         nres = 0
         if pod_req is not None:
             pod_req = self._amounts(pod_req)
@@ -508,19 +517,26 @@ class DeviceContext:
             nres = pod_req.shape[0]
         idx, score, status = self._outputs(p, out)
         cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
-        self._check(fn(
-            self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), nres,
-            N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
+        optional = (N.ptr(pod_group), N.ptr(pod_class)) if classes else (N.ptr(pod_group),)
+        self._check(getattr(self._lib, "msh_" + name)(
+            self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), *optional, nres, N.ptr(pod_req) if nres else None,
+            int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
         return idx, score, status
+
+    def _grouped_device(self, name: str, p, d_pod_digit, d_pod_tol, d_optional, nres, d_pod_req, max_pods_per_node,
+                        d_idx, d_score, d_status, stream) -> None:
+        """msh_<name>_device; d_optional: (d_pod_group,) for a spread form, else (d_pod_group, d_pod_class)."""
+        self._check(getattr(self._lib, f"msh_{name}_device")(
+            self.handle, int(p), d_pod_digit, d_pod_tol, *(d or None for d in d_optional), int(nres), d_pod_req or None,
+            int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
 
     def schedule_sequential_spread_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int, nres: int,
                                           d_pod_req: int, max_pods_per_node: int, d_idx: int, d_score: int,
                                           d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_spread_device (asynchronous on `stream`; d_pod_req and d_pod_group are not
         validated: a group outside [0, G) is an ungrouped pod)."""
-        self._check(self._lib.msh_schedule_sequential_spread_device(
-            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group, int(nres), d_pod_req or None,
-            int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+        self._grouped_device("schedule_sequential_spread", p, d_pod_digit, d_pod_tol, (d_pod_group,),
+                             nres, d_pod_req, max_pods_per_node, d_idx, d_score, d_status, stream)
 
     # -- topology spread together with a resource score (the superset call of the sequential entry points) --
     def seq_spread_scored_max_nodes(self, nres: int = 0) -> int:
@@ -538,17 +554,16 @@ class DeviceContext:
         score. With set_resource_score("least" / "most") the feasible set is schedule_sequential_spread's and a
         feasible node's total is the scored schedule_sequential_fit's (NodeNumber plus weight x the Least /
         MostAllocated score); pod_req is then required. With "none" it is schedule_sequential_spread."""
-        return self._spread_host(self._lib.msh_schedule_sequential_spread_scored, "schedule_sequential_spread_scored",
-                                 pod_digit, pod_tol, pod_group, pod_req, max_pods_per_node, on_commit, out)
+        return self._grouped_host("schedule_sequential_spread_scored", pod_digit, pod_tol, pod_group, None, pod_req,
+                                  max_pods_per_node, on_commit, out, classes=False)
 
     def schedule_sequential_spread_scored_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
                                                  nres: int, d_pod_req: int, max_pods_per_node: int, d_idx: int,
                                                  d_score: int, d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_spread_scored_device (asynchronous on `stream`; d_pod_req and d_pod_group are
         not validated: a group outside [0, G) is an ungrouped pod)."""
-        self._check(self._lib.msh_schedule_sequential_spread_scored_device(
-            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group, int(nres), d_pod_req or None,
-            int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+        self._grouped_device("schedule_sequential_spread_scored", p, d_pod_digit, d_pod_tol, (d_pod_group,),
+                             nres, d_pod_req, max_pods_per_node, d_idx, d_score, d_status, stream)
 
     # -- static node filters: per-class node masks (nodeSelector, required affinity, taints, nodeName) --
     @staticmethod
@@ -604,37 +619,16 @@ class DeviceContext:
         normalizer's extents, the score, the tie-break, the commit) is taken over that feasible set. pod_class None:
         no pod has a class and no column is needed. pod_group None: no pod has a group and no zone column is
         needed."""
-        pod_digit = np.ascontiguousarray(pod_digit, np.int8)
-        pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
-        cols = [pod_digit, pod_tol]
-        if pod_group is not None:
-            pod_group = self._int32s(pod_group, "pod_group")
-            cols.append(pod_group)
-        if pod_class is not None:
-            pod_class = self._int32s(pod_class, "pod_class")
-            cols.append(pod_class)
-        p = _same_len("schedule_sequential_classes", *cols)
-        nres = 0
-        if pod_req is not None:
-            pod_req = self._amounts(pod_req)
-            if pod_req.shape[1] != p:
-                raise ValueError("pod_req is shaped (nres, p)")
-            nres = pod_req.shape[0]
-        idx, score, status = self._outputs(p, out)
-        cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
-        self._check(self._lib.msh_schedule_sequential_classes(
-            self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), N.ptr(pod_class), nres,
-            N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
-        return idx, score, status
+        return self._grouped_host("schedule_sequential_classes", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                  max_pods_per_node, on_commit, out)
 
     def schedule_sequential_classes_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
                                            d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
                                            d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_classes_device (asynchronous on `stream`; d_pod_group and d_pod_class may be 0;
         nothing is validated: a group outside [0, G) is an ungrouped pod, a class outside [0, C) a pod without one)."""
-        self._check(self._lib.msh_schedule_sequential_classes_device(
-            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
-            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+        self._grouped_device("schedule_sequential_classes", p, d_pod_digit, d_pod_tol, (d_pod_group, d_pod_class),
+                             nres, d_pod_req, max_pods_per_node, d_idx, d_score, d_status, stream)
 
     # -- preferred node affinity and PreferNoSchedule scores: per-class raw values --
     def _pref_array(self, a, n_classes: int, width: int, what: str) -> np.ndarray | None:
@@ -703,41 +697,15 @@ class DeviceContext:
         """msh_schedule_sequential_prefs: schedule_sequential_classes with w_affinity * na + w_taint * nt added to
         every feasible node's total, na and nt normalised per pod over its feasible nodes. With both weights 0 it is
         schedule_sequential_classes."""
-        return self._prefs_call("schedule_sequential_prefs", pod_digit, pod_tol, pod_group, pod_class, pod_req,
-                                max_pods_per_node, on_commit, out)
-
-    def _prefs_call(self, name, pod_digit, pod_tol, pod_group, pod_class, pod_req, max_pods_per_node, on_commit, out):
-        """schedule_sequential_prefs, _soft and _balanced: the same arguments, msh_<name>."""
-        pod_digit = np.ascontiguousarray(pod_digit, np.int8)
-        pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
-        cols = [pod_digit, pod_tol]
-        if pod_group is not None:
-            pod_group = self._int32s(pod_group, "pod_group")
-            cols.append(pod_group)
-        if pod_class is not None:
-            pod_class = self._int32s(pod_class, "pod_class")
-            cols.append(pod_class)
-        p = _same_len(name, *cols)
-        nres = 0
-        if pod_req is not None:
-            pod_req = self._amounts(pod_req)
-            if pod_req.shape[1] != p:
-                raise ValueError("pod_req is shaped (nres, p)")
-            nres = pod_req.shape[0]
-        idx, score, status = self._outputs(p, out)
-        cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
-        self._check(getattr(self._lib, "msh_" + name)(
-            self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), N.ptr(pod_group), N.ptr(pod_class), nres,
-            N.ptr(pod_req) if nres else None, int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
-        return idx, score, status
+        return self._grouped_host("schedule_sequential_prefs", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                  max_pods_per_node, on_commit, out)
 
     def schedule_sequential_prefs_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
                                          d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
                                          d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_prefs_device (asynchronous on `stream`; as schedule_sequential_classes_device)."""
-        self._check(self._lib.msh_schedule_sequential_prefs_device(
-            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
-            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+        self._grouped_device("schedule_sequential_prefs", p, d_pod_digit, d_pod_tol, (d_pod_group, d_pod_class),
+                             nres, d_pod_req, max_pods_per_node, d_idx, d_score, d_status, stream)
 
     # -- soft topology spread (whenUnsatisfiable: ScheduleAnyway) --
     def set_spread_group_modes(self, modes) -> None:
@@ -779,16 +747,15 @@ class DeviceContext:
         no spread filter and w_spread * ns is added to every feasible node with a zone, ns upstream's normalised
         PodTopologySpread score over the zones of the pod's feasible nodes. With no such group it is
         schedule_sequential_prefs."""
-        return self._prefs_call("schedule_sequential_soft", pod_digit, pod_tol, pod_group, pod_class, pod_req,
-                                max_pods_per_node, on_commit, out)
+        return self._grouped_host("schedule_sequential_soft", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                  max_pods_per_node, on_commit, out)
 
     def schedule_sequential_soft_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
                                         d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
                                         d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_soft_device (asynchronous on `stream`; as schedule_sequential_prefs_device)."""
-        self._check(self._lib.msh_schedule_sequential_soft_device(
-            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
-            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+        self._grouped_device("schedule_sequential_soft", p, d_pod_digit, d_pod_tol, (d_pod_group, d_pod_class),
+                             nres, d_pod_req, max_pods_per_node, d_idx, d_score, d_status, stream)
 
     # -- NodeResourcesBalancedAllocation --
     def set_balanced_score(self, weight: int = 0) -> None:
@@ -812,16 +779,15 @@ class DeviceContext:
         """msh_schedule_sequential_balanced: schedule_sequential_soft with w_balanced * BS added to every feasible
         node's total, BS upstream's NodeResourcesBalancedAllocation score of the table's first two resources after
         the pod, evaluated in float64 as upstream does. With the weight 0 it is schedule_sequential_soft."""
-        return self._prefs_call("schedule_sequential_balanced", pod_digit, pod_tol, pod_group, pod_class, pod_req,
-                                max_pods_per_node, on_commit, out)
+        return self._grouped_host("schedule_sequential_balanced", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                  max_pods_per_node, on_commit, out)
 
     def schedule_sequential_balanced_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
                                             d_pod_class: int, nres: int, d_pod_req: int, max_pods_per_node: int,
                                             d_idx: int, d_score: int, d_status: int, stream: int = 0) -> None:
         """msh_schedule_sequential_balanced_device (asynchronous on `stream`; as schedule_sequential_soft_device)."""
-        self._check(self._lib.msh_schedule_sequential_balanced_device(
-            self.handle, int(p), d_pod_digit, d_pod_tol, d_pod_group or None, d_pod_class or None, int(nres),
-            d_pod_req or None, int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
+        self._grouped_device("schedule_sequential_balanced", p, d_pod_digit, d_pod_tol, (d_pod_group, d_pod_class),
+                             nres, d_pod_req, max_pods_per_node, d_idx, d_score, d_status, stream)
 
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):

@@ -332,6 +332,32 @@ def test_device_form_without_classes_is_spread_scored(msh, oracle, ctx, mode):
         assert all(np.array_equal(a, b) for a, b in zip(got, outs[0]))
 
 
+@pytest.mark.parametrize("mode", [NONE, LEAST])
+def test_host_form_without_classes_is_spread_scored(msh, oracle, ctx, mode):
+    """The host entry point with pod_class None and groups against _spread_scored on an identically prepared ctx:
+    outputs and the state after the call, over two pod blocks (one of them partial) and a C = 3 column on the ctx."""
+    rng = np.random.default_rng(23 + mode)
+    n, p = 40, 70
+    u, nd, pd, pt = rand_case(rng, n, p)
+    alloc, used, req = rand_amounts(rng, 2, n, p)
+    zone, grp = rng.integers(-1, 3, n), rng.integers(-1, 2, p).astype(np.int32)
+    bits = mask_bits({c: rng.random(n) < 0.5 for c in range(3)})
+    outs = []
+    for entry in ("classes", "spread_scored"):
+        m = Mirror(ctx, msh, oracle, oracle.PluginSet(weights=[3], normalize=[2]), u, nd, zone, [1, 2], alloc, used,
+                   np.full(n, 3), mode, bits=bits, C=3)
+        want = m.expect(pd, pt, grp, None, req)
+        if entry == "classes":
+            got = ctx.schedule_sequential_classes(pd, pt, grp, None, req)
+        else:
+            got = ctx.schedule_sequential_spread_scored(pd, pt, grp, req)
+        m.compare(got, want, entry)
+        m.commit(want)
+        m.verify(entry)
+        outs.append(got)
+    assert all(np.array_equal(a, b) for a, b in zip(*outs))
+
+
 @pytest.mark.parametrize("mode", [NONE, MOST])
 def test_device_form_without_groups_or_zones_is_fit(msh, oracle, ctx, mode):
     """pod_group NULL without a zone column against _fit (mode NONE) and the scored _fit."""
