@@ -1137,6 +1137,151 @@ func (x *Ctx) ScheduleSequentialBalancedDevice(p int, dPodDigit, dPodTol, dGroup
 	return nil
 }
 
+// ---- required inter-pod affinity and anti-affinity ----
+
+// Topologies of an inter-pod affinity term (MSH_TOPOLOGY_*), and the limits of a ctx.
+const (
+	TopologyHostname = 0
+	TopologyZone     = 1
+	MaxAffinityTerms = 32
+	MaxPodProfiles   = 64
+)
+
+func toU32(v []uint32) *C.uint32_t {
+	if len(v) == 0 {
+		return nil
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&v[0]))
+}
+
+// SetPodAffinityTerms sets the terms' topologies (at most MaxAffinityTerms), drops the profiles and zeroes the state;
+// an empty slice is "no terms".
+func (x *Ctx) SetPodAffinityTerms(topo []uint8) error {
+	var p *C.uint8_t
+	if len(topo) > 0 {
+		p = (*C.uint8_t)(unsafe.Pointer(&topo[0]))
+	}
+	if rc := C.msh_set_pod_affinity_terms(x.c, C.int32_t(len(topo)), p); rc != C.MSH_OK {
+		return x.lastErr("msh_set_pod_affinity_terms", rc)
+	}
+	return nil
+}
+
+// PodAffinityTerms returns the terms' topologies.
+func (x *Ctx) PodAffinityTerms() ([]uint8, error) {
+	var t C.int32_t
+	out := make([]uint8, MaxAffinityTerms)
+	if rc := C.msh_get_pod_affinity_terms(x.c, &t, (*C.uint8_t)(unsafe.Pointer(&out[0]))); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_get_pod_affinity_terms", rc)
+	}
+	return out[:int(t)], nil
+}
+
+// SetPodProfiles sets the pod profiles (at most MaxPodProfiles): per profile the terms a pod of it satisfies, its own
+// required anti-affinity terms, and its one required affinity term (-1: none).
+func (x *Ctx) SetPodProfiles(match, anti []uint32, aff []int32) error {
+	if len(match) != len(anti) || len(match) != len(aff) {
+		return errors.New("gpusched: match / anti / aff length mismatch")
+	}
+	if rc := C.msh_set_pod_profiles(x.c, C.int32_t(len(match)), toU32(match), toU32(anti), ptrI32(toI32(aff))); rc != C.MSH_OK {
+		return x.lastErr("msh_set_pod_profiles", rc)
+	}
+	return nil
+}
+
+// PodProfiles returns the profiles (match, anti, aff).
+func (x *Ctx) PodProfiles() (match, anti []uint32, aff []int32, err error) {
+	var q C.int32_t
+	match, anti = make([]uint32, MaxPodProfiles), make([]uint32, MaxPodProfiles)
+	a := make([]C.int32_t, MaxPodProfiles)
+	if rc := C.msh_get_pod_profiles(x.c, &q, toU32(match), toU32(anti), &a[0]); rc != C.MSH_OK {
+		return nil, nil, nil, x.lastErr("msh_get_pod_profiles", rc)
+	}
+	aff = make([]int32, int(q))
+	for i := range aff {
+		aff[i] = int32(a[i])
+	}
+	return match[:int(q)], anti[:int(q)], aff, nil
+}
+
+// UploadPodAffinityState sets the per-node state: present (the OR of the match bits of the pods a node holds) and repel
+// (the OR of their anti-affinity terms), one word per uploaded node each; a nil slice is zeros. UploadNodes zeroes it.
+func (x *Ctx) UploadPodAffinityState(n int, present, repel []uint32) error {
+	if (present != nil && len(present) != n) || (repel != nil && len(repel) != n) {
+		return errors.New("gpusched: one state word per uploaded node")
+	}
+	if rc := C.msh_upload_pod_affinity_state(x.c, C.int32_t(n), toU32(present), toU32(repel)); rc != C.MSH_OK {
+		return x.lastErr("msh_upload_pod_affinity_state", rc)
+	}
+	return nil
+}
+
+// PatchPodAffinityState replaces the whole words of the nodes at idx (distinct List-order indices); a nil slice writes
+// zeros. Pods that were bound before the node snapshot are entered this way.
+func (x *Ctx) PatchPodAffinityState(idx []int32, present, repel []uint32) error {
+	if (present != nil && len(present) != len(idx)) || (repel != nil && len(repel) != len(idx)) {
+		return errors.New("gpusched: idx / state length mismatch")
+	}
+	if rc := C.msh_patch_pod_affinity_state(x.c, C.int32_t(len(idx)), ptrI32(toI32(idx)), toU32(present), toU32(repel)); rc != C.MSH_OK {
+		return x.lastErr("msh_patch_pod_affinity_state", rc)
+	}
+	return nil
+}
+
+// PodAffinityState reads the state of the n uploaded nodes back.
+func (x *Ctx) PodAffinityState(n int) (present, repel []uint32, err error) {
+	present, repel = make([]uint32, n), make([]uint32, n)
+	if rc := C.msh_pod_affinity_state(x.c, toU32(present), toU32(repel)); rc != C.MSH_OK {
+		return nil, nil, x.lastErr("msh_pod_affinity_state", rc)
+	}
+	return present, repel, nil
+}
+
+// SeqPodAffinityMaxNodes returns the largest table ScheduleSequentialPodAffinity takes with nres resources.
+func (x *Ctx) SeqPodAffinityMaxNodes(nres int) (int, error) {
+	var out C.int32_t
+	if rc := C.msh_seq_podaffinity_max_nodes(x.c, C.int32_t(nres), &out); rc != C.MSH_OK {
+		return 0, x.lastErr("msh_seq_podaffinity_max_nodes", rc)
+	}
+	return int(out), nil
+}
+
+// ScheduleSequentialPodAffinity is ScheduleSequentialBalanced with a profile per pod (-1: none): the required
+// inter-pod affinity and anti-affinity filter narrows the feasible set, and each placement is committed to the state
+// before the next pod. A nil profile slice is ScheduleSequentialBalanced.
+func (x *Ctx) ScheduleSequentialPodAffinity(pods []*v1.Pod, b *HostBatch, group, class, profile []int32, nres int,
+	req []int64, maxPodsPerNode int32) ([]Result, error) {
+	if !x.hasNodes {
+		return nil, errors.New("gpusched: UploadNodes has not been called")
+	}
+	p := len(pods)
+	if len(req) != nres*p || (group != nil && len(group) != p) || (class != nil && len(class) != p) ||
+		(profile != nil && len(profile) != p) {
+		return nil, errors.New("gpusched: req holds nres*len(pods) values, group, class and profile len(pods)")
+	}
+	if err := x.pack(b, pods); err != nil {
+		return nil, err
+	}
+	if rc := C.msh_schedule_sequential_podaffinity(x.c, C.int32_t(p), ptrI8(b.pd[:p]), ptrU8(b.pt[:p]), ptrI32(toI32(group)),
+		ptrI32(toI32(class)), ptrI32(toI32(profile)), C.int32_t(nres), ptrI64(toI64(req)), C.int32_t(maxPodsPerNode),
+		ptrI32(b.idx[:p]), ptrI64(b.score[:p]), ptrI32(b.status[:p]), nil, nil); rc != C.MSH_OK {
+		return nil, x.lastErr("msh_schedule_sequential_podaffinity", rc)
+	}
+	return x.results(b), nil
+}
+
+// ScheduleSequentialPodAffinityDevice is the asynchronous form over device pointers
+// (msh_schedule_sequential_podaffinity_device); a profile outside [0, Q) is a pod without one.
+func (x *Ctx) ScheduleSequentialPodAffinityDevice(p int, dPodDigit, dPodTol, dGroup, dClass, dProfile unsafe.Pointer,
+	nres int, dReq unsafe.Pointer, maxPodsPerNode int32, dIdx, dScore, dStatus, stream unsafe.Pointer) error {
+	if rc := C.msh_schedule_sequential_podaffinity_device(x.c, C.int32_t(p), (*C.int8_t)(dPodDigit), (*C.uint8_t)(dPodTol),
+		(*C.int32_t)(dGroup), (*C.int32_t)(dClass), (*C.int32_t)(dProfile), C.int32_t(nres), (*C.int64_t)(dReq),
+		C.int32_t(maxPodsPerNode), (*C.int32_t)(dIdx), (*C.int64_t)(dScore), (*C.int32_t)(dStatus), stream); rc != C.MSH_OK {
+		return x.lastErr("msh_schedule_sequential_podaffinity_device", rc)
+	}
+	return nil
+}
+
 // ---- node sharding (ABI v8): the node table split over GPUs, the cross-shard merge inside the library ----
 //
 // The reference's selectHost keeps the first maximum of the whole List-order node list

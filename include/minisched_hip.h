@@ -757,6 +757,82 @@ int msh_schedule_sequential_balanced_device(msh_ctx* ctx, int32_t p, const int8_
                                             int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
                                             int32_t* d_out_status, void* stream);
 
+/* Required inter-pod affinity and anti-affinity in sequential-commit mode (upstream v1.22,
+ * interpodaffinity/filtering.go: the filter; the preferred, scoring half of the plugin is not implemented;
+ * additive in ABI 8).
+ * Terms. A ctx holds T terms, 0 <= T <= MSH_MAX_AFFINITY_TERMS. A term is a (label selector + namespaces, topology
+ *   key) pair as the host sees it; the device sees its topology alone: MSH_TOPOLOGY_HOSTNAME (the domain is the node
+ *   itself) or MSH_TOPOLOGY_ZONE (the domain is the node's id in the zone column, msh_upload_node_zones; a node
+ *   with zone -1 lacks the key).
+ *   msh_set_pod_affinity_terms(T, topo): sets the terms, drops the profiles and zeroes the state; T = 0 is "no
+ *   terms". T outside [0, 32] or a topo value above 1: MSH_ERR_INVALID. msh_get_pod_affinity_terms reads them back
+ *   (either output may be NULL).
+ * Profiles. A ctx holds Q pod profiles, 0 <= Q <= MSH_MAX_POD_PROFILES. Profile q is match[q] (bit t: a pod of the
+ *   profile satisfies term t by its labels and namespace), anti[q] (the pod's own required anti-affinity terms) and
+ *   aff[q] in [-1, T) (its one required affinity term, -1: none). Upstream counts only the existing pods that match
+ *   all of a pod's affinity terms, so a pod with more than one is not expressible here and must not be approximated.
+ *   msh_set_pod_profiles(Q, match, anti, aff): a bit at or above T, aff outside [-1, T) or Q outside [0, 64]:
+ *   MSH_ERR_INVALID; on a ctx without terms: MSH_ERR_STATE. msh_get_pod_profiles reads them back.
+ * State. Two words per node: present[i], the OR of match over the pods committed to node i, and repel[i], the OR of
+ *   anti over them. Nothing zone-level is stored: a launch derives presentZ[z] / repelZ[z] (the OR over the nodes of
+ *   zone z) and `any` (the OR of present & HM over every node and of present & ZM over the nodes with a zone; HM /
+ *   ZM: the hostname / zone terms) from the words and the zone column as they are.
+ *   msh_upload_pod_affinity_state(n, present, repel): either pointer may be NULL (zeros); n other than the node
+ *   count: MSH_ERR_INVALID. msh_patch_pod_affinity_state(count, idx, present, repel): whole words of nodes idx[k]
+ *   (pairwise distinct, within the table; a NULL array writes zeros). msh_pod_affinity_state reads both columns
+ *   (either output may be NULL). A bit at or above T: MSH_ERR_INVALID; any of the three on a ctx without terms:
+ *   MSH_ERR_STATE. Lifetime and ordering are the class masks' (synchronous, ordered after the sequential launches in
+ *   flight), except that msh_upload_nodes zeroes the state and keeps the terms and profiles; every other writer
+ *   keeps all three.
+ * msh_schedule_sequential_podaffinity / _podaffinity_device take msh_schedule_sequential_balanced's arguments and
+ *   contract with one more per-pod column after pod_class, pod_profile[j] in [-1, Q) (-1: the pod reads and writes
+ *   none of the state). For a pod of profile q with M = match[q], AA = anti[q], AF = aff[q] >= 0 ? 1 << aff[q] : 0,
+ *   and node i with P_i = (present[i] & HM) | (zone[i] >= 0 ? presentZ[zone[i]] & ZM : 0), R_i likewise from repel,
+ *   node i passes when
+ *     (P_i & AA) == 0                                   the pod's own anti-affinity
+ *     (R_i & M) == 0                                    the placed pods' anti-affinity (symmetric)
+ *     AF == 0, or node i has the term's topology key (a zone term fails on a node without a zone) and either
+ *       (P_i & AF) != 0 or the first-pod exception holds: (any & AF) == 0 && (M & AF) != 0.
+ *   The conjunct narrows the feasible set before anything else reads it: the status order, NodeNumber's extents, the
+ *   preference maxima, a soft group's zones, the scores, the first maximum and the commit are taken over what is
+ *   left; the hard spread minimum stays over the zones of the table. No feasible node: MSH_FIT_ERROR. A placed pod
+ *   ORs M into present[sel] and AA into repel[sel], seen by the next pod.
+ *   pod_profile == NULL is _balanced itself: the same kernel, outputs, state and refusals. With a profile column the
+ *   refusals are _balanced's in its order, where the checks that belong to the packed key (the classes' columns, the
+ *   weights' sum with w_spread and w_balanced) always apply and those that belong to the balanced term (a table of
+ *   two resources, every amount within 2^55 in mode NONE) apply with w_balanced > 0 only: the form works with
+ *   w_balanced == 0 and in resource score mode NONE. Then, in this order: no terms or no profiles: MSH_ERR_STATE; a
+ *   zone term on a ctx without a zone column: MSH_ERR_STATE; a launch whose workgroup memory (the node words, 8
+ *   bytes per held node, beside 260 bytes per spread group of the call) would pass 65,536 bytes:
+ *   MSH_ERR_UNSUPPORTED with the largest group count that fits in the message (only a table above 1,024 nodes with
+ *   up to two resources is ever affected: it takes 102 groups of the 128). The host form refuses a profile outside
+ *   [-1, Q) with MSH_ERR_INVALID; the device form treats it as -1. A failed call changes nothing.
+ * Node limits: msh_seq_podaffinity_max_nodes, _balanced's. No other entry point reads the terms, profiles or state. */
+#define MSH_MAX_AFFINITY_TERMS 32
+#define MSH_MAX_POD_PROFILES 64
+#define MSH_TOPOLOGY_HOSTNAME 0
+#define MSH_TOPOLOGY_ZONE 1
+int msh_set_pod_affinity_terms(msh_ctx* ctx, int32_t T, const uint8_t* topo);
+int msh_get_pod_affinity_terms(const msh_ctx* ctx, int32_t* out_T, uint8_t* out_topo);
+int msh_set_pod_profiles(msh_ctx* ctx, int32_t Q, const uint32_t* match, const uint32_t* anti, const int32_t* aff);
+int msh_get_pod_profiles(const msh_ctx* ctx, int32_t* out_Q, uint32_t* out_match, uint32_t* out_anti, int32_t* out_aff);
+int msh_upload_pod_affinity_state(msh_ctx* ctx, int32_t n, const uint32_t* present, const uint32_t* repel);
+int msh_patch_pod_affinity_state(msh_ctx* ctx, int32_t count, const int32_t* idx, const uint32_t* present,
+                                 const uint32_t* repel);
+int msh_pod_affinity_state(msh_ctx* ctx, uint32_t* out_present, uint32_t* out_repel);
+int msh_seq_podaffinity_max_nodes(const msh_ctx* ctx, int32_t nres, int32_t* out_max_nodes);
+int msh_schedule_sequential_podaffinity(msh_ctx* ctx, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                        const int32_t* pod_group, const int32_t* pod_class,
+                                        const int32_t* pod_profile, int32_t nres, const int64_t* pod_req,
+                                        int32_t max_pods_per_node, int32_t* out_idx, int64_t* out_score,
+                                        int32_t* out_status, msh_commit_cb commit_cb, void* user);
+int msh_schedule_sequential_podaffinity_device(msh_ctx* ctx, int32_t p, const int8_t* d_pod_digit,
+                                               const uint8_t* d_pod_tol, const int32_t* d_pod_group,
+                                               const int32_t* d_pod_class, const int32_t* d_pod_profile,
+                                               int32_t nres, const int64_t* d_pod_req, int32_t max_pods_per_node,
+                                               int32_t* d_out_idx, int64_t* d_out_score, int32_t* d_out_status,
+                                               void* stream);
+
 /* ---- node-sharded mode (a cluster's node table split over devices) ----
  * Each shard holds a contiguous slice [node_base, node_base + n) of the global List order and
  * produces int32 keys, key = 0x7FFFFFFF - global_idx (0 = none), so that the element-wise MAX

@@ -62,6 +62,9 @@ MAX_SPREAD_GROUPS = 128  # MSH_MAX_SPREAD_GROUPS
 SPREAD_DO_NOT_SCHEDULE, SPREAD_SCHEDULE_ANYWAY = 0, 1  # MSH_SPREAD_*: a spread group's mode
 SPREAD_SOFT_MAX = 1 << 24  # MSH_SPREAD_SOFT_MAX: counts, pods per call and skews of a SCHEDULE_ANYWAY group
 MAX_POD_CLASSES = 64     # MSH_MAX_POD_CLASSES: pod classes are in [0, C), C <= MAX_POD_CLASSES, -1 = no class
+MAX_AFFINITY_TERMS = 32  # MSH_MAX_AFFINITY_TERMS: the inter-pod affinity terms of a ctx
+MAX_POD_PROFILES = 64    # MSH_MAX_POD_PROFILES: pod profiles are in [0, Q), Q <= MAX_POD_PROFILES, -1 = no profile
+TOPOLOGY_HOSTNAME, TOPOLOGY_ZONE = 0, 1  # MSH_TOPOLOGY_*: a term's topology
 
 MSH_TIEBREAK_FIRST = 0   # the first maximum in List order (the default)
 MSH_TIEBREAK_RANDOM = 1  # seeded uniform choice among the maxima (msh_set_tiebreak)
@@ -94,6 +97,9 @@ EXPORTED = (
     "msh_schedule_sequential_soft_device",
     "msh_set_balanced_score", "msh_balanced_score", "msh_seq_balanced_max_nodes", "msh_schedule_sequential_balanced",
     "msh_schedule_sequential_balanced_device",
+    "msh_set_pod_affinity_terms", "msh_get_pod_affinity_terms", "msh_set_pod_profiles", "msh_get_pod_profiles",
+    "msh_upload_pod_affinity_state", "msh_patch_pod_affinity_state", "msh_pod_affinity_state",
+    "msh_seq_podaffinity_max_nodes", "msh_schedule_sequential_podaffinity", "msh_schedule_sequential_podaffinity_device",
     "msh_shard_keys_len", "msh_shard_keys_device", "msh_decode_keys_device", "msh_keys_slot1_is_any",
     "msh_generic_ext_len", "msh_generic_extents_device", "msh_generic_best_device",
     "msh_generic_candidates_device", "msh_generic_decode_device",
@@ -254,6 +260,16 @@ _SIGS = {
     "msh_seq_balanced_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_schedule_sequential_balanced": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
     "msh_schedule_sequential_balanced_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
+    "msh_set_pod_affinity_terms": (C.c_int, [_P, _I32, _P]),
+    "msh_get_pod_affinity_terms": (C.c_int, [_P, C.POINTER(_I32), _P]),
+    "msh_set_pod_profiles": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "msh_get_pod_profiles": (C.c_int, [_P, C.POINTER(_I32), _P, _P, _P]),
+    "msh_upload_pod_affinity_state": (C.c_int, [_P, _I32, _P, _P]),
+    "msh_patch_pod_affinity_state": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "msh_pod_affinity_state": (C.c_int, [_P, _P, _P]),
+    "msh_seq_podaffinity_max_nodes": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
+    "msh_schedule_sequential_podaffinity": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, COMMIT_CB, _P]),
+    "msh_schedule_sequential_podaffinity_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P, _P, _P]),
     "msh_shard_keys_len": (C.c_int, [_P, _I32, C.POINTER(_I32)]),
     "msh_shard_keys_device": (C.c_int, [_P, _I32, _P, _P, _I64, _P, _P]),
     "msh_decode_keys_device": (C.c_int, [_P, _I32, _P, _P, _P, _P, _P, _P, _P]),

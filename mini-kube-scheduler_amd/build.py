@@ -41,6 +41,7 @@ SOURCES = [
     ("msh_seq_prefs.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_soft.hip", "hipcc", ["-x", "hip"]),
     ("msh_seq_balanced.hip", "hipcc", ["-x", "hip"]),
+    ("msh_seq_podaffinity.hip", "hipcc", ["-x", "hip"]),
     ("msh_prep.hip", "hipcc", ["-x", "hip"]),
     ("msh_capi.cpp", "hipcc", []),
     ("msh_capi_seq.cpp", "hipcc", []),

@@ -263,3 +263,103 @@ def class_key(pod: Any) -> str:
                    _tol_field(t, "effect")] for t in pod_tolerations(pod))
     sel = sorted((str(k), str(v)) for k, v in pod_node_selector(pod).items())
     return json.dumps([pod_node_name(pod), sel, _plain(pod_affinity_terms(pod)), tols], sort_keys=True)
+
+
+# ---- required inter-pod affinity and anti-affinity (the filter half of InterPodAffinity) ----
+
+HOSTNAME_LABEL = "kubernetes.io/hostname"
+_POD_AFFINITY = ("affinity", "podAffinity", "requiredDuringSchedulingIgnoredDuringExecution")
+_POD_ANTI_AFFINITY = ("affinity", "podAntiAffinity", "requiredDuringSchedulingIgnoredDuringExecution")
+
+
+def pod_labels(p: Any) -> Mapping[str, str]:
+    v = p.labels if hasattr(p, "labels") else _get(p, "metadata", "labels")
+    return v or {}
+
+
+def pod_namespace(p: Any) -> str:
+    """metadata.namespace; an object without one is in "default", as the API server would have put it."""
+    v = p.namespace if hasattr(p, "namespace") else _get(p, "metadata", "namespace")
+    return v or "default"
+
+
+def _pod_name(p: Any) -> str:
+    v = p.name if hasattr(p, "name") else _get(p, "metadata", "name")
+    return v or "<unnamed>"
+
+
+def pod_required_pod_affinity(p: Any) -> list:
+    """spec.affinity.podAffinity.requiredDuringSchedulingIgnoredDuringExecution: a list of PodAffinityTerms, empty
+    without one. Attribute objects give pod_affinity_required."""
+    if hasattr(p, "pod_affinity_required"):
+        return list(p.pod_affinity_required or ())
+    return list(_get(p, "spec", *_POD_AFFINITY, default=()) or ())
+
+
+def pod_required_pod_anti_affinity(p: Any) -> list:
+    """spec.affinity.podAntiAffinity.requiredDuringSchedulingIgnoredDuringExecution, as pod_required_pod_affinity.
+    Attribute objects give pod_anti_affinity_required."""
+    if hasattr(p, "pod_anti_affinity_required"):
+        return list(p.pod_anti_affinity_required or ())
+    return list(_get(p, "spec", *_POD_ANTI_AFFINITY, default=()) or ())
+
+
+def label_selector_matches(selector: Any, labels: Mapping[str, str]) -> bool:
+    """apimachinery/pkg/apis/meta/v1/helpers.go: LabelSelectorAsSelector, then labels.Selector.Matches. A nil selector
+    matches nothing, an empty one everything; matchLabels and matchExpressions (In, NotIn, Exists, DoesNotExist) are
+    ANDed. NotIn and DoesNotExist match when the key is absent. Any other operator, In / NotIn without values, or
+    Exists / DoesNotExist with values is invalid there; here it matches nothing."""
+    if selector is None:
+        return False
+    for k, v in (_get(selector, "matchLabels", default=None) or {}).items():
+        if k not in labels or str(labels[k]) != str(v):
+            return False
+    for e in _get(selector, "matchExpressions", default=()) or ():
+        if _get(e, "operator", default="") not in ("In", "NotIn", "Exists", "DoesNotExist"):
+            return False
+        if not _expression_matches(e, labels):
+            return False
+    return True
+
+
+def term_namespaces(term: Any, owner_namespace: str) -> list[str]:
+    """pkg/scheduler/framework/types.go: getNamespacesFromPodAffinityTerm. An empty `namespaces` list (with no
+    namespaceSelector) means the namespace of the pod that owns the term."""
+    ns = [str(x) for x in (_get(term, "namespaces", default=()) or ())]
+    return sorted(set(ns)) if ns else [owner_namespace]
+
+
+def term_matches_pod(term: Any, term_owner_namespace: str, pod: Any) -> bool:
+    """pkg/scheduler/framework/types.go: AffinityTerm.Matches: the pod's namespace is one of the term's and the term's
+    labelSelector matches the pod's labels."""
+    if pod_namespace(pod) not in term_namespaces(term, term_owner_namespace):
+        return False
+    return label_selector_matches(_get(term, "labelSelector", default=None), pod_labels(pod))
+
+
+def term_key(term: Any, owner_namespace: str) -> str:
+    """The canonical form of what term_matches_pod and the topology read from a term: terms with equal keys are one
+    term of the device's table."""
+    return json.dumps([_plain(_get(term, "labelSelector", default=None)), term_namespaces(term, owner_namespace),
+                       _get(term, "topologyKey", default="")], sort_keys=True)
+
+
+def check_pod_affinity(pod: Any, zone_label: str | None) -> tuple[list, list]:
+    """(the pod's required affinity terms, its required anti-affinity terms), after refusing what the device's bit form
+    cannot hold exactly (ValueError naming the pod): a non-empty namespaceSelector, a topologyKey other than
+    kubernetes.io/hostname or the scheduler's zone label, more than one required affinity term (upstream counts only
+    the existing pods that match all of them: one bit per term cannot say that)."""
+    aff, anti = pod_required_pod_affinity(pod), pod_required_pod_anti_affinity(pod)
+    who = f"pod {pod_namespace(pod)}/{_pod_name(pod)}"
+    for t in aff + anti:
+        sel = _get(t, "namespaceSelector", default=None)
+        if sel is not None and (_get(sel, "matchLabels", default=None) or _get(sel, "matchExpressions", default=None)):
+            raise ValueError(f"{who}: a non-empty namespaceSelector in a required pod (anti-)affinity term is not supported")
+        key = _get(t, "topologyKey", default="")
+        if key != HOSTNAME_LABEL and (zone_label is None or key != zone_label):
+            raise ValueError(f"{who}: topologyKey {key!r} is neither {HOSTNAME_LABEL!r} nor the scheduler's zone label "
+                             f"{zone_label!r}")
+    if len(aff) > 1:
+        raise ValueError(f"{who}: {len(aff)} required pod affinity terms; one term per pod is supported (upstream matches "
+                         "an existing pod against all of them at once)")
+    return aff, anti

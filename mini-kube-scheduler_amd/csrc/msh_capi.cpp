@@ -469,6 +469,7 @@ int rewrite(msh_ctx* c, const Rewrite& w) {
     c->h_pref_a.clear();
     c->h_pref_t.clear();
     c->pref_dirty = true;
+    c->pa_have_state = false;  // the inter-pod affinity state: zeros again (the terms and profiles stay)
   }
   c->cur = s;
   c->n_nodes = n;
@@ -859,6 +860,8 @@ void msh_destroy(msh_ctx* c) {
   (void)hipFree(c->d_zone);
   (void)hipFree(c->d_class);
   (void)hipFree(c->d_pref);
+  (void)hipFree(c->d_pa_prof);
+  (void)hipFree(c->d_pa_state);
   (void)hipFree(c->d_skew);
   (void)hipFree(c->d_spread_cnt);
   (void)hipFree(c->d_zone_weight);

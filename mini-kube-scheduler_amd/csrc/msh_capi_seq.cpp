@@ -1,10 +1,10 @@
 // msh_capi_seq.cpp — the grouped sequential-commit entry points of include/minisched_hip.h
-// (msh_schedule_sequential_{spread, spread_scored, classes, prefs, soft, balanced} and their _device forms) and the
-// ctx state only they read: zones, spread groups, modes, weights and counts, the class masks and the class
-// preferences. The plain and resource-fit calls are in msh_capi.cpp, which also holds the helpers both share
-// (msh_ctx.h).
+// (msh_schedule_sequential_{spread, spread_scored, classes, prefs, soft, balanced, podaffinity} and their _device
+// forms) and the ctx state only they read: zones, spread groups, modes, weights and counts, the class masks, the class
+// preferences and the inter-pod affinity terms, profiles and state. The plain and resource-fit calls are in
+// msh_capi.cpp, which also holds the helpers both share (msh_ctx.h).
 //
-// The twelve entry points differ in one thing, the kernel form they launch. Each describes its arguments as a
+// The fourteen entry points differ in one thing, the kernel form they launch. Each describes its arguments as a
 // SeqCall and names the Form it stands for; seq_resolve decides the form that runs, seq_check holds the refusals
 // of all forms in one ordered list, and seq_grouped_device / seq_grouped_host are the one device and host path.
 #include <hip/hip_runtime.h>
@@ -596,6 +596,209 @@ int msh_seq_balanced_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_
   return MSH_OK;
 }
 
+// Required inter-pod affinity (msh_schedule_sequential_podaffinity): the terms and profiles (host copies; the
+// profiles also as the kernel's records on the device) and the per-node state, which is on the device only. The
+// state is the class masks' in ordering: written through prep_stream behind the sequential launches in flight, which
+// read it at their start and write it at their end, and each writer finishes before it returns.
+namespace {
+bool pa_bits_above(uint32_t w, int32_t T) { return T < MSH_MAX_AFFINITY_TERMS && (w >> T) != 0; }
+
+// The device buffers, and the state column valid for the table as it stands: n_pad pairs, zeros where
+// msh_upload_nodes or msh_set_pod_affinity_terms dropped it. Synchronous.
+int pa_state_ready(msh_ctx* c) {
+  if ((size_t)c->n_pad > c->pa_cap) {  // only after an upload of a larger table, which dropped the state
+    uint2* d = nullptr;
+    MSH_HIP(c, hipMalloc(&d, (size_t)c->n_pad * sizeof(uint2)));
+    wait_events(c->seq_inflight);
+    (void)hipFree(c->d_pa_state);
+    c->d_pa_state = d;
+    c->pa_cap = (size_t)c->n_pad;
+    c->pa_have_state = false;
+  }
+  if (c->pa_have_state) return MSH_OK;
+  int rc = after_seq(c);
+  if (rc != MSH_OK) return rc;
+  MSH_HIP(c, hipMemsetAsync(c->d_pa_state, 0, c->pa_cap * sizeof(uint2), c->prep_stream));
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  c->pa_have_state = true;
+  return MSH_OK;
+}
+
+int pa_need_terms(msh_ctx* c) {
+  if (c->pa_terms == 0) return fail(c, MSH_ERR_STATE, "msh_set_pod_affinity_terms has not been called");
+  return MSH_OK;
+}
+
+// the whole column (n_pad pairs) into the page-locked stage
+int pa_state_fetch(msh_ctx* c, uint2** out) {
+  int rc = pa_state_ready(c);
+  if (rc != MSH_OK) return rc;
+  const size_t bytes = (size_t)c->n_pad * sizeof(uint2);
+  if ((rc = node_stage(c, bytes)) != MSH_OK) return rc;
+  if ((rc = after_seq(c)) != MSH_OK) return rc;
+  MSH_HIP(c, hipMemcpyAsync(c->h_nstage, c->d_pa_state, bytes, hipMemcpyDeviceToHost, c->prep_stream));
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  *out = reinterpret_cast<uint2*>(c->h_nstage);
+  return MSH_OK;
+}
+
+// ... and back from it
+int pa_state_store(msh_ctx* c) {
+  const size_t bytes = (size_t)c->n_pad * sizeof(uint2);
+  MSH_HIP(c, hipMemcpyAsync(c->d_pa_state, c->h_nstage, bytes, hipMemcpyHostToDevice, c->prep_stream));
+  MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  return MSH_OK;
+}
+}  // namespace
+
+int msh_set_pod_affinity_terms(msh_ctx* c, int32_t T, const uint8_t* topo) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (T < 0 || T > MSH_MAX_AFFINITY_TERMS) return fail(c, MSH_ERR_INVALID, "T outside [0, MSH_MAX_AFFINITY_TERMS]");
+  if (T > 0 && !topo) return fail(c, MSH_ERR_INVALID, "null topology array");
+  uint32_t hm = 0, zm = 0;
+  for (int32_t t = 0; t < T; ++t) {
+    if (topo[t] > MSH_TOPOLOGY_ZONE)
+      return fail(c, MSH_ERR_INVALID, "topology above MSH_TOPOLOGY_ZONE at term " + std::to_string(t));
+    (topo[t] == MSH_TOPOLOGY_ZONE ? zm : hm) |= uint32_t(1) << t;
+  }
+  c->pa_terms = T;
+  c->h_pa_topo.assign(topo, topo + T);
+  c->pa_host_mask = hm;
+  c->pa_zone_mask = zm;
+  c->pa_profiles = 0;  // the profiles named the old terms
+  c->h_pa_match.clear();
+  c->h_pa_anti.clear();
+  c->h_pa_aff.clear();
+  c->pa_have_state = false;  // and so did the state: zeros, written by the next reader (launches in flight end first)
+  return MSH_OK;
+}
+
+int msh_get_pod_affinity_terms(const msh_ctx* c, int32_t* out_T, uint8_t* out_topo) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_T) *out_T = c->pa_terms;
+  if (out_topo) std::copy(c->h_pa_topo.begin(), c->h_pa_topo.end(), out_topo);
+  return MSH_OK;
+}
+
+int msh_set_pod_profiles(msh_ctx* c, int32_t Q, const uint32_t* match, const uint32_t* anti, const int32_t* aff) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (int rc = pa_need_terms(c); rc != MSH_OK) return rc;
+  if (Q < 0 || Q > MSH_MAX_POD_PROFILES) return fail(c, MSH_ERR_INVALID, "Q outside [0, MSH_MAX_POD_PROFILES]");
+  if (Q > 0 && (!match || !anti || !aff)) return fail(c, MSH_ERR_INVALID, "null profile arrays");
+  const int32_t T = c->pa_terms;
+  for (int32_t q = 0; q < Q; ++q) {
+    if (pa_bits_above(match[q], T) || pa_bits_above(anti[q], T))
+      return fail(c, MSH_ERR_INVALID,
+                  "a bit at or above T = " + std::to_string(T) + " is set at profile " + std::to_string(q));
+    if (aff[q] < -1 || aff[q] >= T)
+      return fail(c, MSH_ERR_INVALID, "affinity term outside [-1, T) at profile " + std::to_string(q));
+  }
+  DeviceGuard g(c->device);
+  int rc = MSH_OK;
+  if (!c->d_pa_prof) MSH_HIP(c, hipMalloc(&c->d_pa_prof, MSH_MAX_POD_PROFILES * sizeof(uint4)));
+  if (Q > 0) {  // the kernel's records, behind the launches in flight, which read the old ones at their start
+    if ((rc = node_stage(c, (size_t)Q * sizeof(uint4))) != MSH_OK) return rc;
+    if ((rc = after_seq(c)) != MSH_OK) return rc;
+    uint4* st = reinterpret_cast<uint4*>(c->h_nstage);
+    for (int32_t q = 0; q < Q; ++q) st[q] = make_uint4(match[q], anti[q], aff[q] >= 0 ? uint32_t(1) << aff[q] : 0u, 0u);
+    MSH_HIP(c, hipMemcpyAsync(c->d_pa_prof, st, (size_t)Q * sizeof(uint4), hipMemcpyHostToDevice, c->prep_stream));
+    MSH_HIP(c, hipStreamSynchronize(c->prep_stream));
+  }
+  c->pa_profiles = Q;
+  c->h_pa_match.assign(match, match + Q);
+  c->h_pa_anti.assign(anti, anti + Q);
+  c->h_pa_aff.assign(aff, aff + Q);
+  return MSH_OK;
+}
+
+int msh_get_pod_profiles(const msh_ctx* c, int32_t* out_Q, uint32_t* out_match, uint32_t* out_anti, int32_t* out_aff) {
+  if (!c) return MSH_ERR_INVALID;
+  if (out_Q) *out_Q = c->pa_profiles;
+  if (out_match) std::copy(c->h_pa_match.begin(), c->h_pa_match.end(), out_match);
+  if (out_anti) std::copy(c->h_pa_anti.begin(), c->h_pa_anti.end(), out_anti);
+  if (out_aff) std::copy(c->h_pa_aff.begin(), c->h_pa_aff.end(), out_aff);
+  return MSH_OK;
+}
+
+int msh_upload_pod_affinity_state(msh_ctx* c, int32_t n, const uint32_t* present, const uint32_t* repel) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (int rc = pa_need_terms(c); rc != MSH_OK) return rc;
+  if (n != c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "state columns of " + std::to_string(n) + " entries for " +
+                                        std::to_string(c->n_nodes) + " uploaded nodes");
+  for (int32_t i = 0; i < n; ++i)
+    if ((present && pa_bits_above(present[i], c->pa_terms)) || (repel && pa_bits_above(repel[i], c->pa_terms)))
+      return fail(c, MSH_ERR_INVALID,
+                  "a bit at or above T = " + std::to_string(c->pa_terms) + " is set at node " + std::to_string(i));
+  DeviceGuard g(c->device);
+  int rc = pa_state_ready(c);
+  if (rc != MSH_OK) return rc;
+  if ((rc = node_stage(c, (size_t)c->n_pad * sizeof(uint2))) != MSH_OK) return rc;
+  if ((rc = after_seq(c)) != MSH_OK) return rc;
+  uint2* st = reinterpret_cast<uint2*>(c->h_nstage);
+  for (int32_t i = 0; i < c->n_pad; ++i)  // the padding slots never hold a node
+    st[i] = i < n ? make_uint2(present ? present[i] : 0u, repel ? repel[i] : 0u) : make_uint2(0u, 0u);
+  rc = pa_state_store(c);
+  if (rc != MSH_OK) c->pa_have_state = false;  // the device column is in an unknown state: zeros
+  return rc;
+}
+
+int msh_patch_pod_affinity_state(msh_ctx* c, int32_t count, const int32_t* idx, const uint32_t* present,
+                                 const uint32_t* repel) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (int rc = pa_need_terms(c); rc != MSH_OK) return rc;
+  if (count < 0) return fail(c, MSH_ERR_INVALID, "negative patch count");
+  if (count == 0) return MSH_OK;
+  if (!idx) return fail(c, MSH_ERR_INVALID, "null patch indices");
+  std::vector<int32_t> sorted(idx, idx + count);
+  std::sort(sorted.begin(), sorted.end());
+  if (sorted.front() < 0 || sorted.back() >= c->n_nodes)
+    return fail(c, MSH_ERR_INVALID, "patch index outside [0, n)");
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+    return fail(c, MSH_ERR_INVALID, "duplicate patch index");
+  for (int32_t k = 0; k < count; ++k)
+    if ((present && pa_bits_above(present[k], c->pa_terms)) || (repel && pa_bits_above(repel[k], c->pa_terms)))
+      return fail(c, MSH_ERR_INVALID, "a bit at or above T = " + std::to_string(c->pa_terms) +
+                                          " is set at patch entry " + std::to_string(k));
+  DeviceGuard g(c->device);
+  // the column through the page-locked stage: read, patched on the host, written back
+  uint2* st = nullptr;
+  int rc = pa_state_fetch(c, &st);
+  if (rc != MSH_OK) return rc;
+  for (int32_t k = 0; k < count; ++k) st[idx[k]] = make_uint2(present ? present[k] : 0u, repel ? repel[k] : 0u);
+  rc = pa_state_store(c);
+  if (rc != MSH_OK) c->pa_have_state = false;
+  return rc;
+}
+
+int msh_pod_affinity_state(msh_ctx* c, uint32_t* out_present, uint32_t* out_repel) {
+  if (!c) return MSH_ERR_INVALID;
+  c->err.clear();
+  if (!c->have_nodes) return fail(c, MSH_ERR_STATE, "msh_upload_nodes has not been called");
+  if (int rc = pa_need_terms(c); rc != MSH_OK) return rc;
+  DeviceGuard g(c->device);
+  uint2* st = nullptr;
+  int rc = pa_state_fetch(c, &st);
+  if (rc != MSH_OK) return rc;
+  for (int32_t i = 0; i < c->n_nodes; ++i) {
+    if (out_present) out_present[i] = st[i].x;
+    if (out_repel) out_repel[i] = st[i].y;
+  }
+  return MSH_OK;
+}
+
+int msh_seq_podaffinity_max_nodes(const msh_ctx* c, int32_t nres, int32_t* out_max_nodes) {
+  if (!c || !out_max_nodes || nres < 0 || nres > MSH_MAX_RESOURCES) return MSH_ERR_INVALID;
+  *out_max_nodes = msh::seq_podaffinity_max_nodes(nres);
+  return MSH_OK;
+}
+
 // The one path of the grouped calls.
 namespace {
 // What every grouped entry point receives. The pointers are device-visible memory in a _device call and host memory
@@ -613,11 +816,13 @@ struct SeqCall {
   int64_t* out_score;
   int32_t* out_status;
   const char* entry = nullptr;  // the name that messages carry (seq_resolve)
+  const int32_t* pod_profile = nullptr;  // msh_schedule_sequential_podaffinity alone; optional
 };
 
 // The kernel forms, in the order the features were stacked: each takes what the one before it takes and adds a term
-// (the resource score, the class masks, the preference scores, the soft spread score, the balanced score).
-enum class Form { Spread, SpreadScored, Classes, Prefs, Soft, Balanced };
+// (the resource score, the class masks, the preference scores, the soft spread score, the balanced score, the
+// inter-pod affinity filter).
+enum class Form { Spread, SpreadScored, Classes, Prefs, Soft, Balanced, PodAffinity };
 
 const char* entry_name(Form f, bool host) {
   static const char* const names[][2] = {
@@ -626,7 +831,8 @@ const char* entry_name(Form f, bool host) {
       {"msh_schedule_sequential_classes_device", "msh_schedule_sequential_classes"},
       {"msh_schedule_sequential_prefs_device", "msh_schedule_sequential_prefs"},
       {"msh_schedule_sequential_soft_device", "msh_schedule_sequential_soft"},
-      {"msh_schedule_sequential_balanced_device", "msh_schedule_sequential_balanced"}};
+      {"msh_schedule_sequential_balanced_device", "msh_schedule_sequential_balanced"},
+      {"msh_schedule_sequential_podaffinity_device", "msh_schedule_sequential_podaffinity"}};
   return names[(int)f][host ? 1 : 0];
 }
 
@@ -636,6 +842,8 @@ const char* entry_name(Form f, bool host) {
 // that callers may have seen in messages and that stay: see the two marked lines.
 Form seq_resolve(Form asked, const msh_ctx* c, SeqCall& k, bool host) {
   Form f = asked, named = asked;
+  // no profile column: _balanced itself. With one the form stays whatever the weights are: its kernel serves them all
+  if (f == Form::PodAffinity && !k.pod_profile) f = named = Form::Balanced;
   if (f == Form::Balanced && c->w_balanced == 0) f = named = Form::Soft;  // no balanced term
   if (f == Form::Soft && c->sp_soft == 0) f = named = Form::Prefs;        // no SCHEDULE_ANYWAY group, whatever w_spread is
   if (f == Form::Prefs && c->w_aff == 0 && c->w_taint == 0) {             // no preference term
@@ -672,10 +880,15 @@ Form seq_resolve(Form asked, const msh_ctx* c, SeqCall& k, bool host) {
 //       Balanced: with the balanced weight
 //   19  Soft, and Balanced on a ctx with a SCHEDULE_ANYWAY group, with groups in the call: the count bound, p and
 //       the soft groups' max_skew above MSH_SPREAD_SOFT_MAX
+//   20  PodAffinity: no terms or no profiles
+//   21  PodAffinity: a zone term and no zone column
+//   22  PodAffinity: the launch's LDS, static and dynamic, above 64 KiB
+// PodAffinity takes Balanced's lines; those of the balanced term itself (11, 12 and 16 in mode NONE) with a nonzero
+// w_balanced only, 19 on a ctx with a SCHEDULE_ANYWAY group.
 // No two of the forms order a pair of these differently, so the guards select lines and never reorder them.
 int seq_check(msh_ctx* c, Form form, const SeqCall& k, bool host) {
   const bool spread = form <= Form::SpreadScored, keyed = form >= Form::Prefs, soft = form >= Form::Soft,
-             balanced = form == Form::Balanced;
+             affine = form == Form::PodAffinity, balanced = form == Form::Balanced || (affine && c->w_balanced > 0);
   const bool grouped = spread || k.pod_group != nullptr, classed = k.pod_class != nullptr;
   const int32_t p = k.p, nres = k.nres;
   const bool null_column = !k.pod_digit || !k.pod_tol || !k.out_idx || !k.out_status || (spread && !k.pod_group);
@@ -731,6 +944,7 @@ int seq_check(msh_ctx* c, Form form, const SeqCall& k, bool host) {
     case Form::Prefs: lim = msh::seq_prefs_max_nodes(nres), what = "preference"; break;
     case Form::Soft: lim = msh::seq_soft_max_nodes(nres), what = "soft-spread"; break;
     case Form::Balanced: lim = msh::seq_balanced_max_nodes(nres), what = "balanced-allocation"; break;
+    case Form::PodAffinity: lim = msh::seq_podaffinity_max_nodes(nres), what = "inter-pod affinity"; break;
   }
   if (c->n_nodes > lim) return fail(c, MSH_ERR_UNSUPPORTED, msh::seq_table_limit_message(what, lim, nres));
   if ((scored || balanced) && c->res_max > MSH_RESOURCE_SCORE_MAX)
@@ -762,7 +976,7 @@ int seq_check(msh_ctx* c, Form form, const SeqCall& k, bool host) {
                                               ": the packed key holds 100 x 655 at most");
   }
   // the counts' bounds belong to the soft groups' term: a balanced call on a ctx without one runs none of it
-  if (soft && k.pod_group && (!balanced || c->sp_soft > 0)) {
+  if (soft && k.pod_group && (form == Form::Soft || c->sp_soft > 0)) {
     const char* above = ", above MSH_SPREAD_SOFT_MAX = 2^24";
     if (c->sp_cnt_bound > MSH_SPREAD_SOFT_MAX)
       return fail(c, MSH_ERR_UNSUPPORTED, "a spread count may have reached " + std::to_string(c->sp_cnt_bound) + above +
@@ -774,6 +988,25 @@ int seq_check(msh_ctx* c, Form form, const SeqCall& k, bool host) {
         return fail(c, MSH_ERR_UNSUPPORTED, "SCHEDULE_ANYWAY group " + std::to_string(g) + " has max_skew " +
                                                 std::to_string(c->h_skew[(size_t)g]) + above);
   }
+  if (!affine) return MSH_OK;
+  if (c->pa_terms == 0)
+    return fail(c, MSH_ERR_STATE, "pod profiles in the call and msh_set_pod_affinity_terms has not been called");
+  if (c->pa_profiles == 0)
+    return fail(c, MSH_ERR_STATE, "pod profiles in the call and msh_set_pod_profiles has not been called");
+  if (c->pa_zone_mask != 0 && !c->have_zone)
+    return fail(c, MSH_ERR_STATE,
+                "an affinity term has the zone topology and msh_upload_node_zones has not been called");
+  // the node words share the workgroup's LDS with the spread counts of the call's groups; no launch opts in to more
+  // than the 64 KiB every kernel may have
+  const int32_t G = k.pod_group ? c->sp_groups : 0;
+  size_t each = 0;
+  const size_t fixed = msh::seq_podaffinity_lds(nres, c->n_nodes, 0, &each);
+  if (fixed + (size_t)G * each > msh::PODAFF_LDS_MAX)
+    return fail(c, MSH_ERR_UNSUPPORTED,
+                std::string(k.entry) + ": " + std::to_string(c->n_nodes) + " nodes with " + std::to_string(nres) +
+                    " resources and " + std::to_string(G) + " spread groups need " +
+                    std::to_string(fixed + (size_t)G * each) + " bytes of workgroup memory, above 65536: at most " +
+                    std::to_string((msh::PODAFF_LDS_MAX - fixed) / each) + " spread groups fit at this table size");
   return MSH_OK;
 }
 
@@ -809,14 +1042,19 @@ int seq_launch(msh_ctx* c, Form form, const SeqCall& k, void* stream) {
   const bool scored = c->rs_mode != MSH_RESOURCE_SCORE_NONE;  // never on Form::Spread: seq_check refused it
   static_assert(msh::SPREAD_SOFT_MAX == MSH_SPREAD_SOFT_MAX, "the kernel's bound is the header's");
   if (form >= Form::Prefs) {  // what the form reads besides the ctx's columns (synchronous, before the block is filled)
-    const int32_t npl = form == Form::Balanced ? msh::seq_balanced_npl(k.nres)
-                                               : (form == Form::Soft ? msh::seq_soft_npl(k.nres) : msh::seq_prefs_npl(k.nres));
+    const int32_t npl = form == Form::PodAffinity ? msh::seq_podaffinity_npl(k.nres)
+                        : form == Form::Balanced  ? msh::seq_balanced_npl(k.nres)
+                        : form == Form::Soft      ? msh::seq_soft_npl(k.nres)
+                                                  : msh::seq_prefs_npl(k.nres);
     if (k.pod_class && (rc = prefs_table(c, npl)) != MSH_OK) return rc;
     if (form >= Form::Soft && (form == Form::Soft || c->sp_soft > 0) && (rc = soft_weights_device(c)) != MSH_OK) return rc;
+    if (form == Form::PodAffinity && (rc = pa_state_ready(c)) != MSH_OK) return rc;
   }
-  // The blocks nest (BalancedArgs > SoftArgs > PrefArgs > SpreadScoreArgs > SpreadArgs): the innermost two are what
-  // the spread and class forms take. Unscored: weight 0, every resource weight 0 and the magic 0, so rs = 0.
-  msh::BalancedArgs ba{};
+  // The blocks nest (PodAffinityArgs > BalancedArgs > SoftArgs > PrefArgs > SpreadScoreArgs > SpreadArgs): the
+  // innermost two are what the spread and class forms take. Unscored: weight 0, every resource weight 0 and the
+  // magic 0, so rs = 0.
+  msh::PodAffinityArgs pq{};
+  msh::BalancedArgs& ba = pq.ba;
   msh::SoftArgs& so = ba.so;
   msh::PrefArgs& pa = so.p;
   msh::SpreadScoreArgs& ss = pa.ss;
@@ -847,6 +1085,7 @@ int seq_launch(msh_ctx* c, Form form, const SeqCall& k, void* stream) {
       case Form::Prefs:
       case Form::Soft:
       case Form::Balanced:
+      case Form::PodAffinity:
         pa.rows = k.pod_class ? c->d_pref : nullptr;
         pa.pod_class = k.pod_class;
         pa.n_classes = k.pod_class ? c->pref_dev_classes : 0;
@@ -864,6 +1103,17 @@ int seq_launch(msh_ctx* c, Form form, const SeqCall& k, void* stream) {
         so.w_spread = (uint32_t)c->w_spread;
         so.zone_weight = c->d_zone_weight;
         ba.w_balanced = (uint32_t)c->w_balanced;
+        if (form == Form::PodAffinity) {
+          pq.state = c->d_pa_state;
+          pq.pod_profile = k.pod_profile;
+          pq.profiles = c->d_pa_prof;
+          pq.n_profiles = c->pa_profiles;
+          pq.host_mask = c->pa_host_mask;
+          pq.zone_mask = c->pa_zone_mask;
+          kernel = "seq_podaffinity_kernel";
+          e = msh::launch_seq_podaffinity(pq, s, &err);
+          break;
+        }
         kernel = form == Form::Balanced ? "seq_balanced_kernel" : "seq_soft_kernel";
         e = form == Form::Balanced ? msh::launch_seq_balanced(ba, s, &err) : msh::launch_seq_soft(so, s, &err);
         break;
@@ -901,25 +1151,32 @@ int seq_grouped_host(msh_ctx* c, Form asked, SeqCall k, msh_commit_cb commit_cb,
     if (k.pod_class[j] < -1 || k.pod_class[j] >= C)
       return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": class " + std::to_string(k.pod_class[j]) +
                                           " outside [-1, C) with C = " + std::to_string(C));
-  if ((rc = check_requests(c, k.nres, p, k.pod_req, c->rs_mode != MSH_RESOURCE_SCORE_NONE, form == Form::Balanced)) != MSH_OK)
+  for (int32_t j = 0; form == Form::PodAffinity && j < p; ++j)
+    if (k.pod_profile[j] < -1 || k.pod_profile[j] >= c->pa_profiles)
+      return fail(c, MSH_ERR_INVALID, "pod " + std::to_string(j) + ": profile " + std::to_string(k.pod_profile[j]) +
+                                          " outside [-1, Q) with Q = " + std::to_string(c->pa_profiles));
+  const bool balanced = form == Form::Balanced || (form == Form::PodAffinity && c->w_balanced > 0);
+  if ((rc = check_requests(c, k.nres, p, k.pod_req, c->rs_mode != MSH_RESOURCE_SCORE_NONE, balanced)) != MSH_OK)
     return rc;
   if (p == 0) return MSH_OK;
   DeviceGuard g(c->device);
   HostIO io;
   if ((rc = host_io_begin(c, p, k.pod_digit, k.pod_tol, k.out_idx, k.out_score, k.out_status, io)) != MSH_OK) return rc;
-  // the requests, the groups and (outside the spread forms, which have none) the classes through the page-locked
-  // node stage, which the kernel reads itself (free here: every writer that uses it has finished its copies, and
-  // this call ends only when the kernel has)
+  // the requests, the groups and (outside the spread forms, which have none) the classes and the profiles through the
+  // page-locked node stage, which the kernel reads itself (free here: every writer that uses it has finished its
+  // copies, and this call ends only when the kernel has)
   const size_t rbytes = (size_t)k.nres * (size_t)p * sizeof(int64_t), cbytes = (size_t)p * sizeof(int32_t);
-  if ((rc = node_stage(c, rbytes + (form <= Form::SpreadScored ? 1 : 2) * cbytes)) != MSH_OK) return rc;
+  if ((rc = node_stage(c, rbytes + (form <= Form::SpreadScored ? 1 : 3) * cbytes)) != MSH_OK) return rc;
   int32_t* sg = reinterpret_cast<int32_t*>(c->h_nstage + rbytes);
   int32_t* sc = reinterpret_cast<int32_t*>(c->h_nstage + rbytes + cbytes);
   if (rbytes) std::memcpy(c->h_nstage, k.pod_req, rbytes);
   if (k.pod_group) std::memcpy(sg, k.pod_group, cbytes);
+  int32_t* sq = reinterpret_cast<int32_t*>(c->h_nstage + rbytes + 2 * cbytes);
   if (k.pod_class) std::memcpy(sc, k.pod_class, cbytes);
+  if (k.pod_profile) std::memcpy(sq, k.pod_profile, cbytes);
   const SeqCall d{p, io.d_pd, io.d_pt, k.pod_group ? sg : nullptr, k.pod_class ? sc : nullptr, k.nres,
                   reinterpret_cast<const int64_t*>(c->h_nstage), k.max_pods_per_node, io.o_idx, io.o_score, io.o_status,
-                  k.entry};
+                  k.entry, k.pod_profile ? sq : nullptr};
   if ((rc = seq_launch(c, form, d, c->stream)) != MSH_OK) return rc;
   if ((rc = host_io_end(c, p, k.out_idx, k.out_score, k.out_status, io)) != MSH_OK) return rc;
   commit_callbacks(commit_cb, user, p, k.out_idx, k.out_score, k.out_status);
@@ -1048,3 +1305,26 @@ int msh_schedule_sequential_balanced(msh_ctx* c, int32_t p, const int8_t* pod_di
   return seq_grouped_host(c, Form::Balanced, k, commit_cb, user);
 }
 
+int msh_schedule_sequential_podaffinity_device(msh_ctx* c, int32_t p, const int8_t* d_pod_digit,
+                                               const uint8_t* d_pod_tol, const int32_t* d_pod_group, const int32_t* d_pod_class,
+                                               const int32_t* d_pod_profile, int32_t nres, const int64_t* d_pod_req,
+                                               int32_t max_pods_per_node, int32_t* d_out_idx, int64_t* d_out_score,
+                                               int32_t* d_out_status, void* stream) {
+  if (!c) return MSH_ERR_INVALID;
+  SeqCall k{p, d_pod_digit, d_pod_tol, d_pod_group, d_pod_class, nres, d_pod_req, max_pods_per_node,
+            d_out_idx, d_out_score, d_out_status};
+  k.pod_profile = d_pod_profile;
+  return seq_grouped_device(c, Form::PodAffinity, k, stream);
+}
+
+int msh_schedule_sequential_podaffinity(msh_ctx* c, int32_t p, const int8_t* pod_digit, const uint8_t* pod_tol,
+                                        const int32_t* pod_group, const int32_t* pod_class, const int32_t* pod_profile,
+                                        int32_t nres, const int64_t* pod_req, int32_t max_pods_per_node,
+                                        int32_t* out_idx, int64_t* out_score, int32_t* out_status,
+                                        msh_commit_cb commit_cb, void* user) {
+  if (!c) return MSH_ERR_INVALID;
+  SeqCall k{p, pod_digit, pod_tol, pod_group, pod_class, nres, pod_req, max_pods_per_node,
+            out_idx, out_score, out_status};
+  k.pod_profile = pod_profile;
+  return seq_grouped_host(c, Form::PodAffinity, k, commit_cb, user);
+}

@@ -152,6 +152,21 @@ struct msh_ctx {
   int32_t pref_dev_classes = 0;
   int64_t pref_stride = 0;
   uint64_t pref_amask = 0, pref_tmask = 0;
+  // required inter-pod affinity (msh_schedule_sequential_podaffinity): the terms' topologies and their masks, the
+  // pod profiles on the host and as the kernel's records in d_pa_prof (MSH_MAX_POD_PROFILES of them, allocated at
+  // first use), and the state, (present, repel) per node, on the device only (every commit changes it): pa_cap pairs,
+  // valid when pa_have_state, else all zero and written as such by the next reader or writer (pa_state_ready).
+  // msh_upload_nodes and msh_set_pod_affinity_terms zero the state by dropping the flag; nothing else does.
+  int32_t pa_terms = 0;
+  std::vector<uint8_t> h_pa_topo;
+  uint32_t pa_host_mask = 0, pa_zone_mask = 0;
+  int32_t pa_profiles = 0;
+  std::vector<uint32_t> h_pa_match, h_pa_anti;
+  std::vector<int32_t> h_pa_aff;
+  uint4* d_pa_prof = nullptr;
+  uint2* d_pa_state = nullptr;
+  size_t pa_cap = 0;
+  bool pa_have_state = false;
   // per caller stream, the event of its last sequential launch: an alias of a table version's reader
   // event (not owned here; track_launch)
   std::vector<std::pair<hipStream_t, hipEvent_t>> seq_inflight;

@@ -403,6 +403,28 @@ struct BalancedArgs {
 int32_t seq_balanced_max_nodes(int32_t nres);
 int32_t seq_balanced_npl(int32_t nres);
 hipError_t launch_seq_balanced(const BalancedArgs& a, hipStream_t s, std::string* err);
+// The inter-pod affinity form (msh_seq_podaffinity.hip, msh_schedule_sequential_podaffinity with a profile column):
+// the balanced-allocation form with the required InterPodAffinity filter as one more conjunct of the feasible set.
+// ba.w_balanced may be 0 (ba.so.p.ss.s.f.nres is then 0..FIT_MAX_RES and the amounts' bound applies only with a
+// resource score). The static and dynamic LDS together must not pass PODAFF_LDS_MAX (checked on the host).
+constexpr int PODAFF_MAX_TERMS = 32;     // MSH_MAX_AFFINITY_TERMS
+constexpr int PODAFF_MAX_PROFILES = 64;  // MSH_MAX_POD_PROFILES
+constexpr size_t PODAFF_LDS_MAX = 65536;
+struct PodAffinityArgs {
+  BalancedArgs ba;
+  uint2* state;               // [n_words * 32] (present, repel): read at the start, written back at the end
+  const int32_t* pod_profile; // [n_pods]: any value outside [0, n_profiles) is a pod without a profile, or null
+  const uint4* profiles;      // [n_profiles] (match, anti, 1 << aff or 0, unused)
+  int32_t n_profiles;         // 0..PODAFF_MAX_PROFILES
+  uint32_t host_mask, zone_mask;  // the terms whose topology is the node / the zone
+};
+// Nodes the kernel holds and its nodes per thread: the balanced-allocation kernel's.
+int32_t seq_podaffinity_max_nodes(int32_t nres);
+int32_t seq_podaffinity_npl(int32_t nres);
+// The LDS bytes of a launch on a table of n_nodes with nres resources and n_groups spread groups in the call, static
+// and dynamic together; *per_group (optional): what one more group adds.
+size_t seq_podaffinity_lds(int32_t nres, int32_t n_nodes, int32_t n_groups, size_t* per_group);
+hipError_t launch_seq_podaffinity(const PodAffinityArgs& a, hipStream_t s, std::string* err);
 // alloc / used [r * stride + idx[k]] = v[r * count + k] for the non-null arrays (device-visible memory)
 hipError_t launch_res_patch(const int32_t* idx, const int64_t* alloc, const int64_t* used, int32_t count, int32_t nres,
                             int64_t stride, int64_t* d_alloc, int64_t* d_used, hipStream_t s);

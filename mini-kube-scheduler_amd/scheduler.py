@@ -496,9 +496,10 @@ class DeviceContext:
                                   max_pods_per_node, on_commit, out, classes=False)
 
     def _grouped_host(self, name: str, pod_digit, pod_tol, pod_group, pod_class, pod_req, max_pods_per_node, on_commit,
-                      out, classes: bool = True):
+                      out, classes: bool = True, extra: tuple = ()):
         """msh_<name>, a host entry point of the grouped sequential calls. classes=False: a spread form, which has
-        no pod_class argument and requires pod_group."""
+        no pod_class argument and requires pod_group. extra: the pointers of further optional per-pod columns, which
+        follow pod_class."""
         pod_digit = np.ascontiguousarray(pod_digit, np.int8)
         pod_tol = np.ascontiguousarray(pod_tol, np.uint8)
         cols = [pod_digit, pod_tol]
@@ -517,7 +518,7 @@ class DeviceContext:
             nres = pod_req.shape[0]
         idx, score, status = self._outputs(p, out)
         cb = N.COMMIT_CB(lambda _u, j, i, s: on_commit(j, i, s)) if on_commit else N.COMMIT_CB()
-        optional = (N.ptr(pod_group), N.ptr(pod_class)) if classes else (N.ptr(pod_group),)
+        optional = ((N.ptr(pod_group), N.ptr(pod_class)) if classes else (N.ptr(pod_group),)) + tuple(extra)
         self._check(getattr(self._lib, "msh_" + name)(
             self.handle, p, N.ptr(pod_digit), N.ptr(pod_tol), *optional, nres, N.ptr(pod_req) if nres else None,
             int(max_pods_per_node), N.ptr(idx), N.ptr(score), N.ptr(status), cb, None))
@@ -525,7 +526,8 @@ class DeviceContext:
 
     def _grouped_device(self, name: str, p, d_pod_digit, d_pod_tol, d_optional, nres, d_pod_req, max_pods_per_node,
                         d_idx, d_score, d_status, stream) -> None:
-        """msh_<name>_device; d_optional: (d_pod_group,) for a spread form, else (d_pod_group, d_pod_class)."""
+        """msh_<name>_device; d_optional: (d_pod_group,) for a spread form, else (d_pod_group, d_pod_class) and for
+        the inter-pod affinity form d_pod_profile after them."""
         self._check(getattr(self._lib, f"msh_{name}_device")(
             self.handle, int(p), d_pod_digit, d_pod_tol, *(d or None for d in d_optional), int(nres), d_pod_req or None,
             int(max_pods_per_node), d_idx, d_score or None, d_status, stream or None))
@@ -789,6 +791,115 @@ class DeviceContext:
         self._grouped_device("schedule_sequential_balanced", p, d_pod_digit, d_pod_tol, (d_pod_group, d_pod_class),
                              nres, d_pod_req, max_pods_per_node, d_idx, d_score, d_status, stream)
 
+    # -- required inter-pod affinity and anti-affinity --
+    @staticmethod
+    def _words32(a, what: str) -> np.ndarray:
+        v = np.asarray(a)
+        if v.ndim != 1 or (v.size and v.dtype.kind not in "iu"):
+            raise ValueError(f"{what}: a one-dimensional integer array")
+        if v.size and (int(v.min()) < 0 or int(v.max()) > 0xFFFFFFFF):
+            raise ValueError(f"{what}: integers within uint32")
+        return np.ascontiguousarray(v, np.uint32)
+
+    def set_pod_affinity_terms(self, topologies=()) -> None:
+        """msh_set_pod_affinity_terms: one topology per term (TOPOLOGY_HOSTNAME or TOPOLOGY_ZONE), at most
+        MAX_AFFINITY_TERMS. Sets the terms, drops the profiles and zeroes the state; an empty list is "no terms"."""
+        t = np.asarray(topologies)
+        if t.ndim != 1 or (t.size and (t.dtype.kind not in "iub" or t.min() < 0 or t.max() > 255)):
+            raise ValueError("topologies is a flat array of 0 / 1")
+        t = np.ascontiguousarray(t, np.uint8)
+        self._check(self._lib.msh_set_pod_affinity_terms(self.handle, len(t), N.ptr(t) if len(t) else None))
+
+    def pod_affinity_terms(self) -> np.ndarray:
+        """msh_get_pod_affinity_terms: the terms' topologies (uint8, one per term)."""
+        n = C.c_int32(0)
+        self._check(self._lib.msh_get_pod_affinity_terms(self.handle, C.byref(n), None))
+        out = np.zeros(n.value, np.uint8)
+        self._check(self._lib.msh_get_pod_affinity_terms(self.handle, C.byref(n), N.ptr(out) if n.value else None))
+        return out
+
+    def set_pod_profiles(self, match=(), anti=(), aff=()) -> None:
+        """msh_set_pod_profiles: per profile the terms a pod of it satisfies (match, a uint32 of term bits), its own
+        required anti-affinity terms (anti) and its one required affinity term (aff, -1: none). At most
+        MAX_POD_PROFILES; the ctx must hold terms."""
+        m, a = self._words32(match, "match"), self._words32(anti, "anti")
+        f = self._int32s(aff, "aff")
+        if not len(m) == len(a) == len(f):
+            raise ValueError("match / anti / aff length mismatch")
+        q = len(m)
+        self._check(self._lib.msh_set_pod_profiles(self.handle, q, N.ptr(m) if q else None, N.ptr(a) if q else None,
+                                                   N.ptr(f) if q else None))
+
+    def pod_profiles(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """msh_get_pod_profiles: (match, anti, aff)."""
+        n = C.c_int32(0)
+        self._check(self._lib.msh_get_pod_profiles(self.handle, C.byref(n), None, None, None))
+        m, a, f = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.int32)
+        if n.value:
+            self._check(self._lib.msh_get_pod_profiles(self.handle, C.byref(n), N.ptr(m), N.ptr(a), N.ptr(f)))
+        return m, a, f
+
+    def upload_pod_affinity_state(self, present=None, repel=None) -> None:
+        """msh_upload_pod_affinity_state: per node (List order) the OR of the match bits (present) and of the
+        anti-affinity terms (repel) of the pods it holds; None: zeros. upload_nodes zeroes the state; every other
+        writer keeps it; only schedule_sequential_podaffinity reads it."""
+        pr = None if present is None else self._words32(present, "present")
+        rp = None if repel is None else self._words32(repel, "repel")
+        for v in (pr, rp):
+            if v is not None and len(v) != self.n_nodes:
+                raise ValueError("one state word per uploaded node")
+        self._check(self._lib.msh_upload_pod_affinity_state(self.handle, self.n_nodes, N.ptr(pr), N.ptr(rp)))
+
+    def patch_pod_affinity_state(self, idx, present=None, repel=None) -> None:
+        """msh_patch_pod_affinity_state: whole words of nodes idx[k] (distinct, within the table); None: zeros."""
+        idx = np.ascontiguousarray(idx, np.int32)
+        pr = None if present is None else self._words32(present, "present")
+        rp = None if repel is None else self._words32(repel, "repel")
+        for v in (pr, rp):
+            if v is not None and len(v) != len(idx):
+                raise ValueError("idx / state length mismatch")
+        self._check(self._lib.msh_patch_pod_affinity_state(self.handle, len(idx), N.ptr(idx), N.ptr(pr), N.ptr(rp)))
+
+    def pod_affinity_state(self) -> tuple[np.ndarray, np.ndarray]:
+        """msh_pod_affinity_state: (present, repel), uint32 per node in List order."""
+        pr, rp = np.zeros(self.n_nodes, np.uint32), np.zeros(self.n_nodes, np.uint32)
+        self._check(self._lib.msh_pod_affinity_state(self.handle, N.ptr(pr) if self.n_nodes else None,
+                                                     N.ptr(rp) if self.n_nodes else None))
+        return pr, rp
+
+    def seq_podaffinity_max_nodes(self, nres: int = 0) -> int:
+        """msh_seq_podaffinity_max_nodes: the largest table schedule_sequential_podaffinity takes with nres (0..4)
+        resources."""
+        out = C.c_int32()
+        self._check(self._lib.msh_seq_podaffinity_max_nodes(self.handle, int(nres), C.byref(out)))
+        return out.value
+
+    def schedule_sequential_podaffinity(self, pod_digit: np.ndarray, pod_tol: np.ndarray, pod_group=None,
+                                        pod_class=None, pod_profile=None, pod_req=None, max_pods_per_node: int = 0,
+                                        on_commit: Callable[[int, int, int], None] | None = None, out=None):
+        """msh_schedule_sequential_podaffinity: schedule_sequential_balanced with a profile per pod (-1: none). A pod
+        of profile q is placed only where the required inter-pod affinity and anti-affinity filter passes: no pod in
+        the node's topology domain matches one of its anti-affinity terms, it matches no anti-affinity term of a pod
+        there, and a pod matching its affinity term is in the domain (or it is the first of a self-affine series).
+        Each placement is committed to the state before the next pod. pod_profile None: schedule_sequential_balanced."""
+        extra = None
+        if pod_profile is not None:
+            extra = self._int32s(pod_profile, "pod_profile")
+            if len(extra) != len(np.asarray(pod_digit)):
+                raise ValueError("schedule_sequential_podaffinity: pod_profile length mismatch")
+        return self._grouped_host("schedule_sequential_podaffinity", pod_digit, pod_tol, pod_group, pod_class, pod_req,
+                                  max_pods_per_node, on_commit, out, extra=(N.ptr(extra),))
+
+    def schedule_sequential_podaffinity_device(self, p: int, d_pod_digit: int, d_pod_tol: int, d_pod_group: int,
+                                               d_pod_class: int, d_pod_profile: int, nres: int, d_pod_req: int,
+                                               max_pods_per_node: int, d_idx: int, d_score: int, d_status: int,
+                                               stream: int = 0) -> None:
+        """msh_schedule_sequential_podaffinity_device (asynchronous on `stream`; as schedule_sequential_balanced_device;
+        a profile outside [0, Q) is a pod without one)."""
+        self._grouped_device("schedule_sequential_podaffinity", p, d_pod_digit, d_pod_tol,
+                             (d_pod_group, d_pod_class, d_pod_profile), nres, d_pod_req, max_pods_per_node, d_idx,
+                             d_score, d_status, stream)
+
     # -- device-resident entry points (integer device addresses, hipStream_t as int) --
     # The per-batch device entry points go through the CPython fast-call module (csrc/msh_pyfast.c):
     # ctypes argument conversion cost ~0.9 us per call next to a ~2.6 us launch.
@@ -1016,6 +1127,21 @@ class Scheduler:
     `resources` with at least two names, the first two being the ones upstream balances (cpu and memory). With a
     nonzero weight every schedule_sequential call is DeviceContext.schedule_sequential_balanced, with the classes,
     groups and requests that the paths above would have passed.
+
+    Required inter-pod affinity and anti-affinity need no configuration: schedule_sequential reads
+    spec.affinity.podAffinity / podAntiAffinity.requiredDuringSchedulingIgnoredDuringExecution of every pod
+    (constraints.check_pod_affinity). The topologyKey of a term is kubernetes.io/hostname (every node is its own
+    domain) or the `zones` label. Per node snapshot the scheduler keeps the distinct terms (at most 32), the profiles
+    of the pods of the call (at most 64: which terms a pod's labels and namespace satisfy, its anti-affinity terms and
+    its one affinity term) and a record of the pods it placed; when a call brings a new term it sets the device's
+    tables again, recomputes the per-node state from the record and uploads it; when it brings only a new profile it
+    sets the profiles alone, which keeps the device's state. Once the snapshot has a term,
+    every pod of every later call gets a profile from its labels and the call is
+    DeviceContext.schedule_sequential_podaffinity with whatever else is configured. Only pods placed by this scheduler
+    against the snapshot are in the record: pods that were bound before it are the caller's to enter through
+    DeviceContext.patch_pod_affinity_state, after the first call that brought the terms and again after any call
+    that brings a new one (the bit of a term is its position in Scheduler.pod_affinity_terms()). The preferred
+    (scoring) half of the plugin is not implemented. schedule_batch ignores all of it.
     """
 
     def __init__(self, filter_plugins: Sequence[str] = (NODE_UNSCHEDULABLE,),
@@ -1087,6 +1213,16 @@ class Scheduler:
         if self.balanced_allocation_weight:
             self.ctx.set_balanced_score(self.balanced_allocation_weight)
         self._tainted: bool | None = None  # a node of the snapshot has a NoSchedule / NoExecute taint (None: not looked yet)
+        self._pa_reset()
+
+    def _pa_reset(self) -> None:
+        """Required inter-pod affinity: the snapshot's terms by constraints.term_key, in the order of their bits, each
+        (term, owner namespace, topology); the profiles on the device by (match, anti, aff); the pods placed against
+        the snapshot as (node index, pod, bits of its anti-affinity terms' keys); whether the device holds the tables."""
+        self._pa_terms: dict[str, tuple[Any, str, int]] = {}
+        self._pa_profiles: dict[tuple[int, int, int], int] = {}
+        self._pa_placed: list[tuple[int, Any, list[str]]] = []
+        self._pa_synced = self._pa_terms_synced = True
 
     @staticmethod
     def _resource_weights(resources, resource_score, resource_weights) -> list[int] | None:
@@ -1129,6 +1265,9 @@ class Scheduler:
         self._node_objs = [nodes[i] for i in self.nodes.order]
         self._class_ids, self._class_masks, self._class_synced, self._tainted = {}, [], False, None
         self._class_aff, self._class_pns, self._class_prefers = [], [], set()
+        if self._pa_terms:
+            self.ctx.set_pod_affinity_terms(())  # the terms belonged to the pods seen against the old snapshot
+        self._pa_reset()
         return self.nodes
 
     def _results(self, pods: PodTable, idx, score, status) -> list[ScheduleResult]:
@@ -1172,7 +1311,20 @@ class Scheduler:
         if self.nodes.allocatable_pods is not None and not self._cap_synced:
             self.ctx.upload_node_capacity(self.nodes.allocatable_pods)
             self._cap_synced = True
+        results = self._schedule_sequential(pods, table, max_pods_per_node)
+        # the record a later inter-pod term is evaluated against: every pod placed against the snapshot
+        for p, r in zip(pods, results):
+            if r.outcome == Outcome.PLACED:
+                ns = K.pod_namespace(p)
+                self._pa_placed.append((r.node_index, p, [K.term_key(t, ns) for t in K.pod_required_pod_anti_affinity(p)]))
+        return results
+
+    def _schedule_sequential(self, pods, table, max_pods_per_node: int) -> list[ScheduleResult]:
+        """The call schedule_sequential makes for what the scheduler is configured with and what the pods ask for."""
         classes = self.pod_class_ids(pods)
+        profiles = self.pod_profile_ids(pods)
+        if profiles is not None:  # the snapshot has an inter-pod term: one call, whatever else is configured
+            return self._schedule_balanced(pods, table, classes, max_pods_per_node, profiles)
         if self.balanced_allocation_weight:  # every pod has the balanced term: one call, whatever else is configured
             return self._schedule_balanced(pods, table, classes, max_pods_per_node)
         if (classes >= 0).any():  # a pod that some node does not admit: the class call, whatever else is configured
@@ -1293,9 +1445,85 @@ class Scheduler:
                                                                   max_pods_per_node)
         return self._results(table, idx, score, status)
 
-    def _schedule_balanced(self, pods, table, classes, max_pods_per_node: int) -> list[ScheduleResult]:
+    def pod_affinity_terms(self) -> list[tuple[Any, str, int]]:
+        """The snapshot's inter-pod terms in the order of their bits: (term, owner namespace, topology)."""
+        return list(self._pa_terms.values())
+
+    def pod_profile_ids(self, pods: Sequence[Any]) -> np.ndarray | None:
+        """A pod's profile for the required inter-pod affinity filter, or None while the snapshot has no term. New
+        terms and profiles are registered (ValueError past 32 terms or 64 profiles, and for what
+        constraints.check_pod_affinity refuses); the device's tables are then set again by the next call."""
+        parsed = [K.check_pod_affinity(p, self.zones) for p in pods]
+        terms_now = dict(self._pa_terms)  # committed only when the whole call is valid: a refused call changes nothing
+        for p, (aff, anti) in zip(pods, parsed):
+            ns = K.pod_namespace(p)
+            for t in aff + anti:
+                key = K.term_key(t, ns)
+                if key not in terms_now:
+                    if len(terms_now) >= N.MAX_AFFINITY_TERMS:
+                        raise ValueError(f"more than {N.MAX_AFFINITY_TERMS} distinct required pod (anti-)affinity terms "
+                                         f"(MAX_AFFINITY_TERMS) against one node snapshot")
+                    topo = N.TOPOLOGY_HOSTNAME if _get(t, "topologyKey") == K.HOSTNAME_LABEL else N.TOPOLOGY_ZONE
+                    terms_now[key] = (t, ns, topo)
+        if not terms_now:
+            return None
+        profiles_before = dict(self._pa_profiles)
+        if len(terms_now) > len(self._pa_terms):  # the profiles' match bits were taken over fewer terms
+            self._pa_terms = terms_now
+            self._pa_profiles = {}
+            self._pa_terms_synced = self._pa_synced = False
+        bit = {key: k for k, key in enumerate(self._pa_terms)}
+        terms = list(self._pa_terms.values())
+        out = np.full(len(pods), -1, np.int32)
+        for j, (p, (aff, anti)) in enumerate(zip(pods, parsed)):
+            ns = K.pod_namespace(p)
+            match = sum(1 << k for k, (t, owner, _) in enumerate(terms) if K.term_matches_pod(t, owner, p))
+            own = sum({1 << bit[K.term_key(t, ns)] for t in anti})
+            af = bit[K.term_key(aff[0], ns)] if aff else -1
+            if not (match or own or af >= 0):
+                continue  # the pod reads and writes nothing of the state
+            prof = (match, own, af)
+            q = self._pa_profiles.get(prof)
+            if q is None:
+                if len(self._pa_profiles) >= N.MAX_POD_PROFILES:
+                    if self._pa_terms_synced:  # no new term: the profiles are again what the device holds
+                        self._pa_profiles = profiles_before
+                    raise ValueError(f"more than {N.MAX_POD_PROFILES} pod profiles (MAX_POD_PROFILES) against one node "
+                                     f"snapshot and term table")
+                q = self._pa_profiles[prof] = len(self._pa_profiles)
+                self._pa_synced = False
+            out[j] = q
+        return out
+
+    def pod_affinity_state(self) -> tuple[np.ndarray, np.ndarray]:
+        """(present, repel) of the pods placed against the snapshot, for the terms as they stand."""
+        n = len(self._node_objs)
+        present, repel = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        bit = {key: k for k, key in enumerate(self._pa_terms)}
+        terms = list(self._pa_terms.values())
+        for i, p, anti_keys in self._pa_placed:
+            present[i] |= sum(1 << k for k, (t, owner, _) in enumerate(terms) if K.term_matches_pod(t, owner, p))
+            repel[i] |= sum({1 << bit[key] for key in anti_keys})
+        return present, repel
+
+    def _sync_pod_affinity(self) -> None:
+        """What changed since the last call, on the device. A new term: the terms, the profiles and the state recomputed
+        from the record (setting the terms zeroes the device's state, the caller's patches with it). New profiles alone:
+        the profiles, which keeps the state."""
+        if self._pa_synced:
+            return
+        if not self._pa_terms_synced:
+            self.ctx.set_pod_affinity_terms([topo for _, _, topo in self._pa_terms.values()])
+        prof = list(self._pa_profiles)
+        self.ctx.set_pod_profiles([m for m, _, _ in prof], [a for _, a, _ in prof], [f for _, _, f in prof])
+        if not self._pa_terms_synced and self._pa_placed:
+            self.ctx.upload_pod_affinity_state(*self.pod_affinity_state())
+        self._pa_synced = self._pa_terms_synced = True
+
+    def _schedule_balanced(self, pods, table, classes, max_pods_per_node: int, profiles=None) -> list[ScheduleResult]:
         """DeviceContext.schedule_sequential_balanced with whatever the scheduler is configured with: the class
-        columns if some pod of the snapshot has a class, the groups with zones, the requests always."""
+        columns if some pod of the snapshot has a class, the groups with zones, the requests always. With profiles:
+        DeviceContext.schedule_sequential_podaffinity."""
         req = self._sync_spread_inputs(pods)
         classed = bool(self._class_masks)
         if classed and not self._class_synced:
@@ -1305,8 +1533,16 @@ class Scheduler:
                                                  np.array(self._class_pns, np.uint16))
             self._class_synced = True
         groups = self.pod_group_ids(pods) if self.zones is not None else None
-        idx, score, status = self.ctx.schedule_sequential_balanced(table.digit, table.tolerates, groups,
-                                                                   classes if classed else None, req, max_pods_per_node)
+        if profiles is None:
+            idx, score, status = self.ctx.schedule_sequential_balanced(table.digit, table.tolerates, groups,
+                                                                       classes if classed else None, req, max_pods_per_node)
+            return self._results(table, idx, score, status)
+        if self.zones is None and any(topo == N.TOPOLOGY_ZONE for _, _, topo in self._pa_terms.values()):
+            raise ValueError("a pod (anti-)affinity term on a zone needs the scheduler's `zones` label")
+        self._sync_pod_affinity()
+        idx, score, status = self.ctx.schedule_sequential_podaffinity(table.digit, table.tolerates, groups,
+                                                                      classes if classed else None, profiles, req,
+                                                                      max_pods_per_node)
         return self._results(table, idx, score, status)
 
     def _schedule_spread(self, pods, table, max_pods_per_node: int) -> list[ScheduleResult]:
