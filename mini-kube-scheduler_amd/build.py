@@ -49,7 +49,7 @@ SOURCES = [
     ("msh_pack.cpp", "g++", []),
 ]
 HEADERS = [CSRC / "msh_internal.h", CSRC / "msh_device.h", CSRC / "msh_pool.h", CSRC / "msh_ctx.h", CSRC / "msh_seq_kernel.h",
-           CSRC / "msh_seq_frame.h", CSRC / "msh_seq_score_policy.h", INCLUDE / "minisched_hip.h"]
+           CSRC / "msh_seq_frame.h", CSRC / "msh_seq_score_policy.h", CSRC / "msh_seq_quot.h", INCLUDE / "minisched_hip.h"]
 
 
 def _hipcc() -> str:
@@ -178,6 +178,29 @@ def build_demo(verbose: bool = False) -> Path:
     return DEMO
 
 
+PROBE_DIR = REPO / "tests" / "probe"
+PROBE = PROBE_DIR / "libmsh_probe.so"
+PROBE_HOST = PROBE_DIR / "libmsh_probe_host.so"
+
+
+def build_probe(verbose: bool = False, device: bool = True, host: bool = True) -> tuple[Path, Path]:
+    """tests/probe: csrc/msh_seq_quot.h's helpers behind plain C entry points for the tests (ctypes): the device
+    probe with the kernels' flags, and a host-only build of the header's integer code. Each is one compile-and-link
+    step, the libraries next to their sources so they travel with the snapshot. `device` / `host` False leaves that
+    library alone (the CPU tests need the host one only, and no device toolchain for it)."""
+    quot = CSRC / "msh_seq_quot.h"
+    flags = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-Wno-unused-value"]
+    for want, lib, src, how in ((device, PROBE, PROBE_DIR / "msh_probe.hip", [f"--offload-arch={ARCH}", *flags, "-x", "hip"]),
+                                (host, PROBE_HOST, PROBE_DIR / "msh_probe_host.cpp", flags)):
+        if want and _stale(lib, [src, quot]):
+            cmd = [_hipcc(), *how, str(src), "-shared", "-o", str(lib)]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            subprocess.run(cmd, check=True)
+    return PROBE, PROBE_HOST
+
+
 if __name__ == "__main__":
     print(build(verbose=True))
     print(build_demo(verbose=True))
+    print(build_probe(verbose=True))

@@ -13,6 +13,7 @@
 
 #include "../../include/minisched_hip.h"
 #include "msh_internal.h"
+#include "msh_seq_quot.h"
 
 // One version of the node-side device tables (List order, padded to cap nodes).
 struct NodeTable {
@@ -297,7 +298,7 @@ void resource_score_setting(const msh_ctx* c, int32_t nres, A& a) {
   a.weight = c->rs_weight;
   uint32_t sum = 0;
   for (int32_t r = 0; r < msh::FIT_MAX_RES; ++r) sum += (uint32_t)(a.rw[r] = r < nres ? c->rs_w[r] : 0);
-  a.wsum_magic = (uint32_t)(((uint64_t(1) << 31) + sum - 1) / sum);
+  a.wsum_magic = msh::wsum_magic(sum);
 }
 // The requests of a host call, [nres][p]: each within [0, 2^62]; with a resource score (scored), then with the
 // balanced score, within 2^55.

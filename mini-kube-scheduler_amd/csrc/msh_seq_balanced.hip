@@ -1,8 +1,8 @@
 // msh_seq_balanced.hip — the balanced-allocation form of the sequential-commit kernel
 // (msh_schedule_sequential_balanced with a nonzero w_balanced): the soft-spread form (msh_seq_soft.hip) with upstream's
 // NodeResourcesBalancedAllocation score (v1.22, pkg/scheduler/framework/plugins/noderesources/balanced_allocation.go,
-// volumes off) as one more term of the key's sum. The soft-spread kernel is not edited for it: its quotients, score
-// policy, per-pod record and step are repeated here (quot_u16s, soft_raw, quot_soft, BalScore, BalRow) and the step
+// volumes off) as one more term of the key's sum. The soft-spread kernel is not edited for it: its score policy,
+// per-pod record and step are repeated here (BalScore, BalRow; the quotients are msh_seq_quot.h's) and the step
 // below is its step plus what follows. See msh_seq_soft.hip for the phases, the slots and the barriers; nothing of
 // them changes.
 // Per pod j and held node i, with r in {0, 1} the table's first two resources:
@@ -24,56 +24,6 @@
 #include "msh_seq_score_policy.h"
 
 namespace msh {
-
-// 100 * a / m for 0 <= a <= 65,535, 1 <= m <= 65,535, rm = 1 / m as a float (any rounding within a few ulp):
-// 100 * a < 2^24 is exact in a float, the product is within 1 of the quotient, one correction step either way.
-// Only the quotients of feasible nodes are used, where a <= m.
-__device__ __forceinline__ uint32_t quot_u16s(uint32_t a, uint32_t m, float rm) {
-  const uint32_t num = 100u * a;
-  uint32_t q = (uint32_t)((float)num * rm);
-  const int32_t r = (int32_t)num - (int32_t)(q * m);  // in [-m, 2m)
-  q += r >= (int32_t)m ? 1u : 0u;
-  q -= r < 0 ? 1u : 0u;
-  return q;
-}
-
-// raw_z of msh_seq_soft.hip's head comment for a count c in [0, 2^25], w = log(size + 2) <= log 66 and
-// skew1 = max_skew - 1 in [0, 2^24): the product and the sum rounded separately (contraction off: no fused
-// multiply-add), then half away from zero. y < 2^28 and y - trunc(y) is exact, so the comparison with 0.5 is Go's
-// math.Round.
-__device__ __forceinline__ int32_t soft_raw(int32_t c, double w, int32_t skew1) {
-#pragma clang fp contract(off)
-  const double x = (double)c * w;
-  const double y = x + (double)skew1;
-  const double t = __builtin_trunc(y);
-  return (int32_t)t + (y - t >= 0.5 ? 1 : 0);
-}
-
-// 100 * a / m, truncated, for 0 <= a <= m, 1 <= m < 2^28 (the bound of raw above; MSH_SPREAD_SOFT_MAX keeps it),
-// rm = 1 / float(m) within an ulp. The true quotient x is in [0, 100]; float(a), the factor 100, float(m), the
-// reciprocal and the product each err by at most 2^-23 relative, so the estimate is within 100 * 5 * 2^-23 < 2^-14
-// of x and its floor is floor(x) or one off, and only next to an integer. The remainder is taken in 64 bits
-// (100 * a < 2^35, q * m <= 101 * 2^28) and corrects one step either way: exact.
-__device__ __forceinline__ uint32_t quot_soft(uint32_t a, uint32_t m, float rm) {
-  uint32_t q = (uint32_t)((float)a * 100.0f * rm);
-  const int64_t r = (int64_t)(100ull * a) - (int64_t)((uint64_t)q * m);  // in [-m, 2m)
-  q += r >= (int64_t)m ? 1u : 0u;
-  q -= r < 0 ? 1u : 0u;
-  return q;
-}
-
-// BS of the head comment for 0 <= q_r <= 2^56 and 0 <= c_r <= 2^55: two conversions and one division per resource,
-// the clamp, then v_add_f64 (the difference), v_add_f64 (1 - |d|, the modulus an operand modifier), v_mul_f64 and
-// a truncating convert. f_r is in [0, 1], so the product is in [0, 100].
-__device__ __forceinline__ uint32_t balanced_bs(int64_t q0, int64_t c0, int64_t q1, int64_t c1) {
-#pragma clang fp contract(off)
-  const double x0 = (double)q0 / (double)c0, x1 = (double)q1 / (double)c1;
-  const double f0 = (c0 == 0 || x0 > 1.0) ? 1.0 : x0;
-  const double f1 = (c1 == 0 || x1 > 1.0) ? 1.0 : x1;
-  const double d = f0 - f1;
-  const double u = 1.0 - __builtin_fabs(d);
-  return (uint32_t)(int32_t)(u * 100.0);
-}
 
 template <int NR, int NPL, bool MOST>
 struct BalScore : ScoreArgmax<NR, NPL, MOST> {
@@ -112,7 +62,7 @@ struct BalScore : ScoreArgmax<NR, NPL, MOST> {
         const uint32_t s = quot100(num, c, 100.0f * __builtin_amdgcn_rcpf((float)(double)c));
         acc += (none ? 0u : s) * this->rw[r];
       }
-    return __umulhi(acc * 2u, this->magic) * wres;
+    return wsum_div(acc, this->magic) * wres;
   }
 
   // BS of node k: q_r = used + request = alloc - free + request for the table's first two resources
@@ -373,7 +323,7 @@ __global__ __launch_bounds__(NW * WAVE) void seq_balanced_kernel(BalancedArgs ba
         const float ra = __builtin_amdgcn_rcpf((float)da), rt = __builtin_amdgcn_rcpf((float)dt);
 #pragma unroll
         for (int k = 0; k < NPL; ++k)
-          sum[k] = w_aff * quot_u16s(row[k] & 0xFFFFu, da, ra) + w_taint * (100u - quot_u16s(row[k] >> 16, dt, rt));
+          sum[k] = w_aff * quot_u16(row[k] & 0xFFFFu, da, ra) + w_taint * (100u - quot_u16(row[k] >> 16, dt, rt));
       } else {
 #pragma unroll
         for (int k = 0; k < NPL; ++k) sum[k] = w_taint * 100u;

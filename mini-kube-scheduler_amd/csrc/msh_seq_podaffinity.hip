@@ -35,45 +35,6 @@
 namespace msh {
 namespace {
 
-// 100 * a / m for 0 <= a <= 65,535, 1 <= m <= 65,535, rm = 1 / m as a float (see msh_seq_balanced.hip)
-__device__ __forceinline__ uint32_t pa_quot_u16s(uint32_t a, uint32_t m, float rm) {
-  const uint32_t num = 100u * a;
-  uint32_t q = (uint32_t)((float)num * rm);
-  const int32_t r = (int32_t)num - (int32_t)(q * m);  // in [-m, 2m)
-  q += r >= (int32_t)m ? 1u : 0u;
-  q -= r < 0 ? 1u : 0u;
-  return q;
-}
-
-// raw_z of msh_seq_soft.hip's head comment: the product and the sum rounded separately, then half away from zero
-__device__ __forceinline__ int32_t pa_soft_raw(int32_t c, double w, int32_t skew1) {
-#pragma clang fp contract(off)
-  const double x = (double)c * w;
-  const double y = x + (double)skew1;
-  const double t = __builtin_trunc(y);
-  return (int32_t)t + (y - t >= 0.5 ? 1 : 0);
-}
-
-// 100 * a / m, truncated, for 0 <= a <= m, 1 <= m < 2^28 (see msh_seq_balanced.hip)
-__device__ __forceinline__ uint32_t pa_quot_soft(uint32_t a, uint32_t m, float rm) {
-  uint32_t q = (uint32_t)((float)a * 100.0f * rm);
-  const int64_t r = (int64_t)(100ull * a) - (int64_t)((uint64_t)q * m);  // in [-m, 2m)
-  q += r >= (int64_t)m ? 1u : 0u;
-  q -= r < 0 ? 1u : 0u;
-  return q;
-}
-
-// BS of msh_seq_balanced.hip's head comment, every operation rounded once
-__device__ __forceinline__ uint32_t pa_balanced_bs(int64_t q0, int64_t c0, int64_t q1, int64_t c1) {
-#pragma clang fp contract(off)
-  const double x0 = (double)q0 / (double)c0, x1 = (double)q1 / (double)c1;
-  const double f0 = (c0 == 0 || x0 > 1.0) ? 1.0 : x0;
-  const double f1 = (c1 == 0 || x1 > 1.0) ? 1.0 : x1;
-  const double d = f0 - f1;
-  const double u = 1.0 - __builtin_fabs(d);
-  return (uint32_t)(int32_t)(u * 100.0);
-}
-
 // BalScore of msh_seq_balanced.hip
 template <int NR, int NPL, bool MOST>
 struct PaScore : ScoreArgmax<NR, NPL, MOST> {
@@ -107,13 +68,13 @@ struct PaScore : ScoreArgmax<NR, NPL, MOST> {
         const uint32_t s = quot100(num, c, 100.0f * __builtin_amdgcn_rcpf((float)(double)c));
         acc += (none ? 0u : s) * this->rw[r];
       }
-    return __umulhi(acc * 2u, this->magic) * wres;
+    return wsum_div(acc, this->magic) * wres;
   }
 
   __device__ __forceinline__ uint32_t balanced(const FrameNodes<NR, NPL>& n, const FramePod<NR>& pod, int k) const {
     static_assert(NR >= 2, "the balanced score reads two resources");
     const int64_t c0 = this->al[0][k], c1 = this->al[1][k];
-    return pa_balanced_bs(c0 - n.fr[0][k] + pod.rq[0], c0, c1 - n.fr[1][k] + pod.rq[1], c1);
+    return balanced_bs(c0 - n.fr[0][k] + pod.rq[0], c0, c1 - n.fr[1][k] + pod.rq[1], c1);
   }
 
   __device__ __forceinline__ void decode(const uint32_t (&v)[K], uint32_t pc, int32_t* sel, int64_t* sc,
@@ -421,7 +382,7 @@ __global__ __launch_bounds__(NW * WAVE) void seq_podaffinity_kernel(PodAffinityA
         const float ra = __builtin_amdgcn_rcpf((float)da), rt = __builtin_amdgcn_rcpf((float)dt);
 #pragma unroll
         for (int k = 0; k < NPL; ++k)
-          sum[k] = w_aff * pa_quot_u16s(row[k] & 0xFFFFu, da, ra) + w_taint * (100u - pa_quot_u16s(row[k] >> 16, dt, rt));
+          sum[k] = w_aff * quot_u16(row[k] & 0xFFFFu, da, ra) + w_taint * (100u - quot_u16(row[k] >> 16, dt, rt));
       } else {
 #pragma unroll
         for (int k = 0; k < NPL; ++k) sum[k] = w_taint * 100u;
@@ -439,11 +400,11 @@ __global__ __launch_bounds__(NW * WAVE) void seq_podaffinity_kernel(PodAffinityA
         const double w = sh.lw[__builtin_popcountll(zs)];  // a uniform address: one broadcast read
         const bool in_zs = ((zs >> lane) & 1ull) != 0;
         // the counts are read behind the phase's barrier, not before it: one register less across the wait
-        const int32_t raw = pa_soft_raw(lcnt[pg * SPREAD_ZONES + lane], w, -skew - 1);
+        const int32_t raw = soft_raw(lcnt[pg * SPREAD_ZONES + lane], w, -skew - 1);
         const int32_t mx = wave_reduce(in_zs ? raw : 0, [](int32_t x, int32_t y) { return max(x, y); });
         const int32_t mn = wave_reduce(in_zs ? raw : INT32_MAX, [](int32_t x, int32_t y) { return min(x, y); });
         const uint32_t dm = (uint32_t)max(mx, 1);
-        const uint32_t q = pa_quot_soft((uint32_t)(mx + mn - (in_zs ? raw : mn)), dm, __builtin_amdgcn_rcpf((float)dm));
+        const uint32_t q = quot_soft((uint32_t)(mx + mn - (in_zs ? raw : mn)), dm, __builtin_amdgcn_rcpf((float)dm));
         const int32_t ns = in_zs ? (int32_t)(mx == 0 ? 100u : q) : 0;  // lane z: zone z's normalised score
 #pragma unroll
         for (int k = 0; k < NPL; ++k) {

@@ -33,18 +33,6 @@
 
 namespace msh {
 
-// 100 * a / m for 0 <= a <= 65,535, 1 <= m <= 65,535, rm = 1 / m as a float (any rounding within a few ulp):
-// 100 * a < 2^24 is exact in a float, the product is within 1 of the quotient, one correction step either way.
-// Only the quotients of feasible nodes are used, where a <= m.
-__device__ __forceinline__ uint32_t quot_u16(uint32_t a, uint32_t m, float rm) {
-  const uint32_t num = 100u * a;
-  uint32_t q = (uint32_t)((float)num * rm);
-  const int32_t r = (int32_t)num - (int32_t)(q * m);  // in [-m, 2m)
-  q += r >= (int32_t)m ? 1u : 0u;
-  q -= r < 0 ? 1u : 0u;
-  return q;
-}
-
 template <int NR, int NPL, bool MOST>
 struct PrefScore : ScoreArgmax<NR, NPL, MOST> {
   using Base = ScoreArgmax<NR, NPL, MOST>;
@@ -79,7 +67,7 @@ struct PrefScore : ScoreArgmax<NR, NPL, MOST> {
         const uint32_t s = quot100(num, c, this->rc[r][k]);
         acc += (none ? 0u : s) * this->rw[r];
       }
-    return __umulhi(acc * 2u, this->magic) * wres;
+    return wsum_div(acc, this->magic) * wres;
   }
 
   // ScoreArgmax::decode with the key's sum taken as it is

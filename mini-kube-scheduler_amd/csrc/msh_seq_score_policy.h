@@ -7,19 +7,9 @@
 #pragma once
 
 #include "msh_seq_frame.h"
+#include "msh_seq_quot.h"
 
 namespace msh {
-
-// num * 100 / c for 0 <= num <= c, 1 <= c <= 2^55, rc = 100 / c rounded to float.
-__device__ __forceinline__ uint32_t quot100(int64_t num, int64_t c, float rc) {
-  const uint32_t lo = (uint32_t)((uint64_t)num & 0xFFFFFFFFull), hi = (uint32_t)((uint64_t)num >> 32);
-  const float nf = __builtin_fmaf((float)hi, 4294967296.0f, (float)lo);
-  uint32_t s = (uint32_t)(nf * rc);                           // within 1 of the quotient
-  const int64_t rm = num * 100 - (int64_t)(uint64_t)s * c;  // in [-c, 2c)
-  s += rm >= c ? 1u : 0u;
-  s -= rm < 0 ? 1u : 0u;
-  return s;
-}
 
 template <int NR, int NPL, bool MOST>
 struct ScoreArgmax : FramePolicy {
@@ -74,7 +64,7 @@ struct ScoreArgmax : FramePolicy {
           acc += (none ? 0u : s) * rw[r];
         }
       }
-      const uint32_t rs = __umulhi(acc * 2u, magic);  // acc / sum of the weights
+      const uint32_t rs = wsum_div(acc, magic);  // acc / sum of the weights
       const uint32_t key = ok ? (((rs + 1u) << 16) | (kbase - (uint32_t)k)) : 0u;
       const bool mt = ((n.codes >> (4 * k)) & 15u) == pod.pc;
       km = umax(km, mt ? key : 0u);

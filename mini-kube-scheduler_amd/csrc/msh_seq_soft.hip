@@ -2,8 +2,8 @@
 // with a SCHEDULE_ANYWAY group): the preference form (msh_seq_prefs.hip) with the scoring half of upstream's
 // PodTopologySpread (pkg/scheduler/framework/plugins/podtopologyspread/scoring.go, one constraint per group, the
 // zone key) for the pods of a soft group. The preference kernel is not edited for it: its per-pod record, score
-// policy and quotient are repeated here (SoftRow, SoftScore, quot_u16s) and the step below is its step plus what
-// follows. A group's mode travels in the sign of its max_skew in LDS (SoftArgs::soft; negative: soft).
+// policy are repeated here (SoftRow, SoftScore; the quotients are msh_seq_quot.h's) and the step below is its step plus
+// what follows. A group's mode travels in the sign of its max_skew in LDS (SoftArgs::soft; negative: soft).
 // Per pod of a soft group g (workgroup-uniform, as the group is):
 //  1. no spread filter: the hard groups' `allowed` ballot is skipped and hz is not ANDed into pod.av, so the feasible
 //     set F is an ungrouped pod's and nodes without a zone stay in it;
@@ -30,42 +30,6 @@
 #include "msh_seq_score_policy.h"
 
 namespace msh {
-
-// 100 * a / m for 0 <= a <= 65,535, 1 <= m <= 65,535, rm = 1 / m as a float (any rounding within a few ulp):
-// 100 * a < 2^24 is exact in a float, the product is within 1 of the quotient, one correction step either way.
-// Only the quotients of feasible nodes are used, where a <= m.
-__device__ __forceinline__ uint32_t quot_u16s(uint32_t a, uint32_t m, float rm) {
-  const uint32_t num = 100u * a;
-  uint32_t q = (uint32_t)((float)num * rm);
-  const int32_t r = (int32_t)num - (int32_t)(q * m);  // in [-m, 2m)
-  q += r >= (int32_t)m ? 1u : 0u;
-  q -= r < 0 ? 1u : 0u;
-  return q;
-}
-
-// raw_z of the head comment for a count c in [0, 2^25], w = log(size + 2) <= log 66 and skew1 = max_skew - 1 in
-// [0, 2^24): the product and the sum rounded separately (contraction off: no fused multiply-add), then half away
-// from zero. y < 2^28 and y - trunc(y) is exact, so the comparison with 0.5 is Go's math.Round.
-__device__ __forceinline__ int32_t soft_raw(int32_t c, double w, int32_t skew1) {
-#pragma clang fp contract(off)
-  const double x = (double)c * w;
-  const double y = x + (double)skew1;
-  const double t = __builtin_trunc(y);
-  return (int32_t)t + (y - t >= 0.5 ? 1 : 0);
-}
-
-// 100 * a / m, truncated, for 0 <= a <= m, 1 <= m < 2^28 (the bound of raw above; MSH_SPREAD_SOFT_MAX keeps it),
-// rm = 1 / float(m) within an ulp. The true quotient x is in [0, 100]; float(a), the factor 100, float(m), the
-// reciprocal and the product each err by at most 2^-23 relative, so the estimate is within 100 * 5 * 2^-23 < 2^-14
-// of x and its floor is floor(x) or one off, and only next to an integer. The remainder is taken in 64 bits
-// (100 * a < 2^35, q * m <= 101 * 2^28) and corrects one step either way: exact.
-__device__ __forceinline__ uint32_t quot_soft(uint32_t a, uint32_t m, float rm) {
-  uint32_t q = (uint32_t)((float)a * 100.0f * rm);
-  const int64_t r = (int64_t)(100ull * a) - (int64_t)((uint64_t)q * m);  // in [-m, 2m)
-  q += r >= (int64_t)m ? 1u : 0u;
-  q -= r < 0 ? 1u : 0u;
-  return q;
-}
 
 template <int NR, int NPL, bool MOST>
 struct SoftScore : ScoreArgmax<NR, NPL, MOST> {
@@ -101,7 +65,7 @@ struct SoftScore : ScoreArgmax<NR, NPL, MOST> {
         const uint32_t s = quot100(num, c, this->rc[r][k]);
         acc += (none ? 0u : s) * this->rw[r];
       }
-    return __umulhi(acc * 2u, this->magic) * wres;
+    return wsum_div(acc, this->magic) * wres;
   }
 
   // ScoreArgmax::decode with the key's sum taken as it is
@@ -344,7 +308,7 @@ __global__ __launch_bounds__(NW * WAVE) void seq_soft_kernel(SoftArgs so) {
         const float ra = __builtin_amdgcn_rcpf((float)da), rt = __builtin_amdgcn_rcpf((float)dt);
 #pragma unroll
         for (int k = 0; k < NPL; ++k)
-          sum[k] = w_aff * quot_u16s(row[k] & 0xFFFFu, da, ra) + w_taint * (100u - quot_u16s(row[k] >> 16, dt, rt));
+          sum[k] = w_aff * quot_u16(row[k] & 0xFFFFu, da, ra) + w_taint * (100u - quot_u16(row[k] >> 16, dt, rt));
       } else {
 #pragma unroll
         for (int k = 0; k < NPL; ++k) sum[k] = w_taint * 100u;
