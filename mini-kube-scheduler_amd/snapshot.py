@@ -55,7 +55,7 @@ def node_allocatable_pods(n: Any) -> int | None:
     return v
 
 
-_QUANTITY = re.compile(r"^([+-]?)(\d*)(?:\.(\d*))?(m|k|M|G|T|P|E|Ki|Mi|Gi|Ti|Pi|Ei)?$")
+_QUANTITY = re.compile(r"^([+-]?)(\d*)(?:\.(\d*))?(?:[eE]([+-]?\d+)|(m|k|M|G|T|P|E|Ki|Mi|Gi|Ti|Pi|Ei))?$")
 _SUFFIX = {None: (1, 1), "m": (1, 1000),
            **{s: (1000 ** (k + 1), 1) for k, s in enumerate(("k", "M", "G", "T", "P", "E"))},
            **{s: (1024 ** (k + 1), 1) for k, s in enumerate(("Ki", "Mi", "Gi", "Ti", "Pi", "Ei"))}}
@@ -65,7 +65,8 @@ RESOURCE_MAX = N.RESOURCE_MAX
 def parse_quantity(s: Any, milli: bool = False) -> int:
     """A k8s resource.Quantity as an integer: its Value(), or with milli=True its MilliValue(), both rounded up
     as upstream does ("1m" is 1 as a value, "0.5" is 500 milli). Accepts integers, plain and decimal numbers and
-    the suffixes m k M G T P E Ki Mi Gi Ti Pi Ei; exact integer arithmetic. Anything else raises ValueError."""
+    the suffixes m k M G T P E Ki Mi Gi Ti Pi Ei, or in their place a decimal exponent ("12e6", "1E3", "5e-1"); exact
+    integer arithmetic. Anything else raises ValueError."""
     if isinstance(s, bool):
         raise ValueError(f"not a quantity: {s!r}")
     if isinstance(s, int):
@@ -73,8 +74,13 @@ def parse_quantity(s: Any, milli: bool = False) -> int:
     m = _QUANTITY.match(s.strip()) if isinstance(s, str) else None
     if m is None or not (m.group(2) or m.group(3)):
         raise ValueError(f"not a quantity: {s!r}")
-    sign, whole, frac, suffix = m.group(1), m.group(2) or "0", m.group(3) or "", m.group(4)
+    sign, whole, frac, suffix = m.group(1), m.group(2) or "0", m.group(3) or "", m.group(5)
     mul, div = _SUFFIX[suffix]
+    if m.group(4) is not None:
+        exp = int(m.group(4))
+        if abs(exp) > 40:  # far outside what an amount within [0, 2^62] can need
+            raise ValueError(f"not a quantity: {s!r}")
+        mul, div = (10 ** exp, 1) if exp >= 0 else (1, 10 ** -exp)
     num = int(whole + frac) * mul * (1000 if milli else 1)
     den = 10 ** len(frac) * div
     if sign == "-":
