@@ -49,7 +49,8 @@ SOURCES = [
     ("msh_pack.cpp", "g++", []),
 ]
 HEADERS = [CSRC / "msh_internal.h", CSRC / "msh_device.h", CSRC / "msh_pool.h", CSRC / "msh_ctx.h", CSRC / "msh_seq_kernel.h",
-           CSRC / "msh_seq_frame.h", CSRC / "msh_seq_score_policy.h", CSRC / "msh_seq_quot.h", INCLUDE / "minisched_hip.h"]
+           CSRC / "msh_seq_frame.h", CSRC / "msh_seq_score_policy.h", CSRC / "msh_seq_quot.h", CSRC / "msh_generic_norm.h",
+           INCLUDE / "minisched_hip.h"]
 
 
 def _hipcc() -> str:
@@ -184,16 +185,22 @@ PROBE_HOST = PROBE_DIR / "libmsh_probe_host.so"
 
 
 def build_probe(verbose: bool = False, device: bool = True, host: bool = True) -> tuple[Path, Path]:
-    """tests/probe: csrc/msh_seq_quot.h's helpers behind plain C entry points for the tests (ctypes): the device
-    probe with the kernels' flags, and a host-only build of the header's integer code. Each is one compile-and-link
-    step, the libraries next to their sources so they travel with the snapshot. `device` / `host` False leaves that
-    library alone (the CPU tests need the host one only, and no device toolchain for it)."""
-    quot = CSRC / "msh_seq_quot.h"
+    """tests/probe: the kernels' pure helpers behind plain C entry points for the tests (ctypes). The device probe,
+    with the kernels' flags, is every .hip source of tests/probe in one library: msh_probe.hip runs
+    csrc/msh_seq_quot.h's helpers over their documented domains, and msh_gprobe.hip runs csrc/msh_generic_norm.h
+    (generic_kernel's NormalizeScore by reciprocal at every divisor in [1, 2^32], the full domain, for the three
+    modes and key types; its terms, masks and maximum) and msh_device.h's decodes and bit helpers. The host library
+    is a host-only build of msh_seq_quot.h's integer code and of msh_generic_norm.h's double paths. Each is one
+    compile-and-link step, the libraries next to their sources so they travel with the snapshot. `device` / `host`
+    False leaves that library alone (the CPU tests need the host one only, and no device toolchain for it)."""
+    heads = [CSRC / "msh_seq_quot.h", CSRC / "msh_generic_norm.h", *sorted(PROBE_DIR.glob("*.h"))]
     flags = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", "-Wno-unused-value"]
-    for want, lib, src, how in ((device, PROBE, PROBE_DIR / "msh_probe.hip", [f"--offload-arch={ARCH}", *flags, "-x", "hip"]),
-                                (host, PROBE_HOST, PROBE_DIR / "msh_probe_host.cpp", flags)):
-        if want and _stale(lib, [src, quot]):
-            cmd = [_hipcc(), *how, str(src), "-shared", "-o", str(lib)]
+    for want, lib, srcs, deps, how in (
+            (device, PROBE, sorted(PROBE_DIR.glob("*.hip")), [*heads, CSRC / "msh_device.h", CSRC / "msh_internal.h"],
+             [f"--offload-arch={ARCH}", *flags, "-x", "hip"]),
+            (host, PROBE_HOST, [PROBE_DIR / "msh_probe_host.cpp"], heads, flags)):
+        if want and _stale(lib, [*srcs, *deps]):
+            cmd = [_hipcc(), *how, *map(str, srcs), "-shared", "-o", str(lib)]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)

@@ -32,6 +32,7 @@
 // each pod's extents over this shard's nodes (ext, mins negated: one all-reduce MAX merges them), MODE 2
 // takes the merged extents and writes each pod's best (total, global node index) over the shard.
 #include "msh_device.h"
+#include "msh_generic_norm.h"
 
 namespace msh {
 
@@ -39,62 +40,11 @@ constexpr int GEN_W = 8;       // waves per workgroup
 constexpr int GEN_BPW = 2;     // 64-pod blocks per wave: one LDS read of a node serves both
 constexpr int GEN_CHUNK = 16;  // nodes per first-maximum chunk
 constexpr uint32_t GEN_CODE_NONE = 10u;  // a node name without a suffix digit (matches no pod's code)
-constexpr double GEN_RCP_BIAS = 1.0 + 0x1p-49;
 // two nodes' staged values per LDS read: ds_read_b128 moves 16 B per lane in 4 LDS cycles, where the
 // ds_read2_b64 the compiler forms from two 8-B reads takes 8 (MI355X_MICROARCH.md §LDS)
 typedef uint32_t gen_u4 __attribute__((ext_vector_type(4)));
 typedef double gen_d2 __attribute__((ext_vector_type(2)));
 constexpr uint32_t GEN_NONE = 0xFFFFFFFFu;
-
-// NormalizeScore of one raw score given the pod's extent of that plugin over its feasible nodes
-// (mx, mn): upstream helper.DefaultNormalizeScore(MaxNodeScore = 100, reverse) — maxCount starts at 0,
-// an all-zero list is left alone (reverse: all 100) — or min-max (0 when max == min).
-__device__ __forceinline__ int64_t gen_normalize(int64_t raw, int32_t mode, int64_t mx, int64_t mn) {
-  switch (mode) {
-    case 1: {
-      const int64_t m = mx > 0 ? mx : 0;
-      return m == 0 ? raw : 100 * raw / m;
-    }
-    case 2: {
-      const int64_t m = mx > 0 ? mx : 0;
-      return m == 0 ? 100 : 100 - 100 * raw / m;
-    }
-    case 3: return mx == mn ? 0 : (raw - mn) * 100 / (mx - mn);
-    default: return raw;
-  }
-}
-
-// v_max_f64 as the instruction (fmax adds a NaN canonicalisation per operand): IEEE mode,
-// a quiet NaN operand yields the other one
-__device__ __forceinline__ double vmax_f64(double a, double b) {
-  double r;
-  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-// v with its high dword ORed with m: m all-ones turns it into a quiet NaN (exponent and quiet bit set)
-__device__ __forceinline__ double nan_if(double v, uint32_t x, uint32_t nt) {
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t hi = bop3_or_and((uint32_t)(b >> 32), x, nt);
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | (uint32_t)b);
-}
-
-// Per-pair key of the main pass (KT): uint32_t (32-bit totals, biased by 2^31) or uint64_t (biased by
-// 2^63), 0 = infeasible; or double (the total, |total| < 2^53), NaN = infeasible (v_max_f64 skips it).
-template <int KT>
-using GKey = typename std::conditional<KT == 0, uint32_t,
-                                       typename std::conditional<KT == 1, uint64_t, double>::type>::type;
-
-template <int KT>
-__device__ __forceinline__ GKey<KT> key_mask(GKey<KT> t, uint32_t xm, uint32_t nt) {
-  if constexpr (KT == 2) {
-    return nan_if(t, xm, nt);
-  } else if constexpr (KT == 1) {
-    const uint32_t lo = bop3_andn_of_and((uint32_t)t, xm, nt), hi = bop3_andn_of_and((uint32_t)(t >> 32), xm, nt);
-    return ((uint64_t)hi << 32) | lo;
-  } else {
-    return bop3_andn_of_and(t, xm, nt);
-  }
-}
 
 // One lane's scoring state of one 64-pod block (main pass): NodeNumber's weighted normalized value on a
 // digit match / otherwise, biased (the score columns' part is the node's class term, staged per tile).
@@ -102,28 +52,6 @@ template <int KT>
 struct GLane {
   GKey<KT> k1, k0;
 };
-
-// The contribution of normalizing column c to a pair's total: w x trunc((v - b) x r), v = 100 x raw.
-template <int KT, bool SUB>
-__device__ __forceinline__ GKey<KT> col_term(double v, double b, double r, GKey<KT> cw) {
-  const double q = (SUB ? v - b : v) * r;
-  if constexpr (KT == 2) {
-    // |trunc(q) x w| is within the host's 2^53 bound on a feasible pair: exact (the others are masked)
-    return __builtin_trunc(q) * cw;
-  } else if constexpr (KT == 1) {
-    // |q| < 2^40 on a feasible pair; an infeasible pair's value is clamped, converted and masked out
-    const int64_t n = (int64_t)__builtin_fmin(__builtin_fmax(q, -0x1p62), 0x1p62);
-    return (uint64_t)n * cw;
-  } else {
-    // |n| and |w| below 2^23 on a feasible pair (the host's bound, GenericArgs::w64): the signed 24-bit
-    // multiply (full rate, where v_mul_lo_u32 is quarter rate); v_cvt_i32_f64 saturates on the others.
-    // That operand range is guaranteed ONLY by generic_args' c24 check (msh_capi.cpp): every normalizing
-    // column's weight and normalized-score bound below 2^23, else the launch takes 64-bit keys. A new term
-    // multiplied here must be added to that check.
-    const int32_t n = (int32_t)q;
-    return (uint32_t)__mul24(n, (int32_t)cw);
-  }
-}
 
 template <int MODE, int KT, bool TS, int NNC, bool MMX>
 __global__ __launch_bounds__(GEN_W * WAVE) void generic_kernel(GenericArgs a) {
@@ -398,18 +326,8 @@ __global__ __launch_bounds__(GEN_W * WAVE) void generic_kernel(GenericArgs a) {
       const int32_t md = a.nmode[c];
       const int64_t mx = emx[b][1 + c], mn = emn[b][1 + c];
       if (mx == INT64_MIN) continue;  // no feasible node
-      double rr = 0.0, bb = 0.0;
-      if (md == 3) {                  // min-max: (raw - mn) x 100 / (mx - mn), 0 when mx == mn
-        if (mx != mn) {
-          rr = (1.0 / (double)(mx - mn)) * GEN_RCP_BIAS;
-          bb = 100.0 * (double)mn;
-        }
-      } else {  // DefaultNormalizeScore: 100 raw / max(mx, 0); DEFAULT leaves an all-zero list (m = 0 -> raw)
-        const int64_t m = mx > 0 ? mx : 0;
-        if (m != 0) rr = (1.0 / (double)m) * GEN_RCP_BIAS;
-        else if (md == 1) rr = 0.01 * GEN_RCP_BIAS;
-        // REVERSE with m == 0: r = 0, 100 - 0 = 100 for every node
-      }
+      double rr, bb;
+      gen_norm_params(md, mx, mn, &rr, &bb);
       s_crr[kc][c] = rr;
       s_cbb[kc][c] = bb;
     }

@@ -10,19 +10,16 @@
 //   [last] the inputs evaluated: the host checks it against the size of the domain
 // The *_raw entry points return the helper's outputs for inputs chosen by the host, which judges them itself.
 // Every entry point returns 0 or the hipError_t that stopped it.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
 #include "../../mini-kube-scheduler_amd/csrc/msh_seq_quot.h"
+#include "msh_probe_common.h"
 
 namespace {
+
+using namespace probe;
 
 constexpr int REP_TUPLES = 8;
 constexpr int REP_WORDS = 4 + 4 * REP_TUPLES + 2;
 constexpr int REP_OFFERED = REP_WORDS - 2, REP_SEEN = REP_WORDS - 1;
-constexpr int TPB = 256;
-typedef unsigned long long u64;
 
 // One thread's tallies, added to the report once at its end; a mismatch's tuple is taken while fewer than
 // REP_TUPLES are recorded (rep[REP_OFFERED] counts them).
@@ -198,37 +195,6 @@ __global__ __launch_bounds__(TPB) void k_balanced_bs(const int64_t* q, int64_t n
 }
 
 // ---- host plumbing ----
-#define PROBE_TRY(x)                 \
-  do {                               \
-    const hipError_t e_ = (x);       \
-    if (e_ != hipSuccess) return e_; \
-  } while (0)
-
-struct Dev {  // device buffers of one call, freed on every way out
-  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-  int n = 0;
-  ~Dev() {
-    for (int i = 0; i < n; ++i) (void)hipFree(p[i]);
-  }
-  hipError_t get(void** out, size_t bytes) {
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipSuccess) p[n++] = *out;
-    return e;
-  }
-  hipError_t put(void** out, const void* src, size_t bytes) {
-    const hipError_t e = get(out, bytes);
-    return e != hipSuccess ? e : hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice);
-  }
-};
-
-unsigned blocks(int64_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-
-hipError_t finish(void* host, const void* dev, size_t bytes) {
-  PROBE_TRY(hipGetLastError());
-  PROBE_TRY(hipDeviceSynchronize());
-  return hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
-}
-
 hipError_t new_report(Dev& d, u64** rep) {
   PROBE_TRY(d.get((void**)rep, REP_WORDS * sizeof(u64)));
   return hipMemset(*rep, 0, REP_WORDS * sizeof(u64));
