@@ -10,8 +10,8 @@ Status, NodeNumber's normalizer extents, the resource score (modes LEAST / MOST;
 maximum in List order and the commit are taken over that set; a class does not change what a commit writes, and the
 spread minimum stays over Zset.
 
-1. `serial`: a plain Python triple loop (pod, node, resource) in Python ints. Tiny shapes.
-2. `per_pod`: written separately, one pod at a time with the nodes in numpy int64.
+`serial` (a plain Python loop over pods, nodes and resources in Python ints, tiny shapes) and `per_pod` (one pod at a
+time with the nodes in numpy int64) are seq_ref's two loops with every later feature left absent.
 Neither forms an availability mask or packs keys: a node's verdict is read from bits[i] >> c & 1 directly.
 
 Arguments are spread_score_ref.serial's up to rw, then (bits, n_classes, pod_class); zone, group and pod_class may be
@@ -38,151 +38,25 @@ def clean_classes(pod_class, n_classes: int, p: int) -> list[int]:
     return [int(c) if 0 <= int(c) < n_classes else -1 for c in pod_class]
 
 
+def _column(bits, n: int):
+    """Here an absent column admits no node to any class (from prefs_ref on it admits every node)."""
+    return np.zeros(n, np.uint64) if bits is None else bits
+
+
 def serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group, max_skew,
            mode, weight, rw, bits, n_classes, pod_class, counts=None, cnt=None):
-    n, p = len(unsched), len(pod_digit)
-    assert n * p <= 2 * 10**5, "the serial loop is for tiny shapes"
-    nres, G = len(alloc), len(max_skew)
-    eff = [int(x) for x in eff]
-    count = [0] * n if counts is None else [int(x) for x in counts]
-    al = [[int(x) for x in row] for row in alloc]
-    us = [[int(x) for x in row] for row in used]
-    rw = [int(x) for x in rw]
-    zn = [-1] * n if zone is None else [int(z) for z in zone]
-    zs = sorted({z for z in zn if z >= 0})
-    sk = [int(x) for x in max_skew]
-    c = [[0] * MAX_ZONES for _ in range(G)] if cnt is None else [[int(x) for x in row] for row in cnt]
-    grp = [-1] * p if group is None else [int(g) if 0 <= int(g) < G else -1 for g in group]
-    cls = clean_classes(pod_class, n_classes, p)
-    word = [int(b) for b in bits] if bits is not None else [0] * n
-    has_nu = "NodeUnschedulable" in plugins.filters
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    for j in range(p):
-        pd, tol, g, k = int(pod_digit[j]), bool(pod_tol[j]), grp[j], cls[j]
-        rq = [int(req[r][j]) for r in range(nres)]
-        feas = []
-        for i in range(n):
-            if k >= 0 and not (word[i] >> k) & 1:
-                continue
-            if has_nu and unsched[i] and not tol:
-                continue
-            if not count[i] < eff[i]:
-                continue
-            fits = True
-            for r in range(nres):
-                if rq[r] > 0 and rq[r] > al[r][i] - us[r][i]:
-                    fits = False
-            if not fits:
-                continue
-            if g >= 0:
-                if zn[i] < 0:
-                    continue
-                if c[g][zn[i]] + 1 - min(c[g][z] for z in zs) > sk[g]:
-                    continue
-            feas.append(i)
-        if not feas:
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):  # NodeNumber.Score finds no PreScore state
-            status[j] = SCORE_ERROR
-            continue
-        total = [0] * len(feas)
-        for w, nm in zip(plugins.weights, plugins.normalize):
-            raw = [10 if 0 <= int(node_digit[i]) == pd else 0 for i in feas]
-            total = [O._wrap64(t + s * int(w)) for t, s in zip(total, O.normalize(int(nm), raw))]
-        if mode != NONE:
-            for m, i in enumerate(feas):
-                rs = RS.resource_score(mode, [al[r][i] for r in range(nres)], [us[r][i] + rq[r] for r in range(nres)], rw)
-                total[m] = O._wrap64(total[m] + int(weight) * rs)
-        best = max(total)
-        sel = feas[total.index(best)]  # the first maximum in List order
-        idx[j], score[j] = sel, best
-        count[sel] += 1
-        for r in range(nres):
-            us[r][sel] += rq[r]
-        if g >= 0:
-            c[g][zn[sel]] += 1
-    return (idx, score, status, np.array(count, np.int32), np.array(us, np.int64).reshape(nres, n),
-            np.array(c, np.int32).reshape(G, MAX_ZONES))
+    import seq_ref
+    return seq_ref.serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
+                          max_skew, mode, weight, rw, _column(bits, len(unsched)), n_classes, pod_class, counts=counts,
+                          cnt=cnt)
 
 
 def per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group, max_skew,
             mode, weight, rw, bits, n_classes, pod_class, counts=None, cnt=None):
-    n, p = len(unsched), len(pod_digit)
-    alloc = np.asarray(alloc, np.int64).reshape(-1, n)
-    us = np.array(used, np.int64).reshape(-1, n)
-    req = np.asarray(req, np.int64).reshape(-1, p)
-    nres, G = alloc.shape[0], len(max_skew)
-    if mode != NONE:
-        assert max(alloc.max(initial=0), us.max(initial=0), req.max(initial=0)) <= RS.SCORE_MAX, "int64 would overflow"
-        rw = np.asarray(rw, np.int64)
-        scored = [r for r in range(nres) if rw[r] > 0]
-        den = int(rw[scored].sum())
-        safe = np.where(alloc == 0, 1, alloc)
-    eff = np.asarray(eff, np.int64)
-    count = np.zeros(n, np.int64) if counts is None else np.array(counts, np.int64)
-    nd = np.asarray(node_digit, np.int64)
-    zn = np.full(n, -1, np.int64) if zone is None else np.asarray(zone, np.int64)
-    zs = np.unique(zn[zn >= 0])
-    zsafe = np.where(zn >= 0, zn, 0)
-    sk = np.asarray(max_skew, np.int64)
-    c = np.zeros((G, MAX_ZONES), np.int64) if cnt is None else np.array(cnt, np.int64).reshape(G, MAX_ZONES)
-    grp = np.full(p, -1, np.int64) if group is None else np.asarray(group, np.int64)
-    cls = np.full(p, -1, np.int64) if pod_class is None else np.asarray(pod_class, np.int64)
-    word = np.zeros(n, np.uint64) if bits is None else np.asarray(bits, np.uint64)
-    blocked = np.asarray(unsched, bool) if "NodeUnschedulable" in plugins.filters else np.zeros(n, bool)
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    lowest = np.iinfo(np.int64).min
-    for j in range(p):
-        pd = int(pod_digit[j])
-        g = int(grp[j]) if 0 <= grp[j] < G else -1
-        k = int(cls[j]) if 0 <= cls[j] < n_classes else -1
-        feas = count < eff
-        if not pod_tol[j]:
-            feas = feas & ~blocked
-        if k >= 0:
-            feas = feas & ((word >> np.uint64(k)) & np.uint64(1)).astype(bool)
-        for r in range(nres):
-            if req[r, j] > 0:
-                feas = feas & (alloc[r] - us[r] >= req[r, j])
-        if g >= 0:
-            if len(zs) == 0:
-                feas = np.zeros(n, bool)
-            else:
-                feas = feas & (zn >= 0) & (c[g][zsafe] - c[g][zs].min() < sk[g])
-        if not feas.any():
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):
-            status[j] = SCORE_ERROR
-            continue
-        total = np.zeros(n, np.int64)
-        raw = np.where((nd == pd) & (nd >= 0), 10, 0).astype(np.int64)
-        for w, nm in zip(plugins.weights, plugins.normalize):
-            total = total + RS._nn_scores(int(nm), raw, feas) * np.int64(O._wrap64(int(w)))
-        if mode != NONE:
-            acc = np.zeros(n, np.int64)
-            for r in scored:
-                q = us[r] + req[r, j]
-                part = (alloc[r] - q) if mode == LEAST else q
-                none = (alloc[r] == 0) | (q > alloc[r])
-                acc += np.where(none, 0, np.where(none, 0, part) * 100 // safe[r]) * rw[r]
-            total = total + (acc // den) * np.int64(O._wrap64(int(weight)))
-        sel = int(np.argmax(np.where(feas, total, lowest)))  # argmax returns the first maximum
-        idx[j], score[j] = sel, total[sel]
-        count[sel] += 1
-        us[:, sel] += req[:, j]
-        if g >= 0:
-            c[g, zn[sel]] += 1
-    return idx, score, status, count.astype(np.int32), us, c.astype(np.int32)
+    import seq_ref
+    return seq_ref.per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
+                           max_skew, mode, weight, rw, _column(bits, len(unsched)), n_classes, pod_class, counts=counts,
+                           cnt=cnt)
 
 
 DENSITIES = ("none", "one", "tenth", "half", "all")

@@ -13,17 +13,15 @@ node i passes when (P_i & AA) == 0 (own anti), (R_i & M) == 0 (symmetric anti) a
 term's topology key and (P_i & AF) != 0 or the first-pod exception holds, (any & AF) == 0 and (M & AF) != 0. A placed
 pod ORs M into present[sel] and AA into repel[sel]. A pod of profile -1 reads and writes none of it.
 
-`State` carries present / repel between calls; `per_pod` is balanced_ref.per_pod's loop, node-vectorised in numpy, with
-the conjunct, and counts why nodes were rejected and how often the exception admitted a pod (`stats`): a node is
-counted under the first of own anti, symmetric anti, missing topology key, affinity that rejects it, among the nodes
-the other filters left. `gen_case` is the seeded generator of the GPU tests."""
+`State` carries present / repel between calls; `per_pod` is seq_ref.per_pod, the loop of every layer node-vectorised in
+numpy, which applies `conjunct` to the nodes the other filters left and commits into the state. `conjunct` counts why
+nodes were rejected, and the loop how often the exception admitted a pod (`stats`): a node is counted under the first of
+own anti, symmetric anti, missing topology key, affinity that rejects it, among the nodes the other filters left. `gen_case` is the seeded generator of the GPU tests."""
 from __future__ import annotations
 
 import numpy as np
 
 import balanced_ref as BR
-import resource_score_ref as RS
-import soft_spread_ref as SR
 
 NONE, LEAST, MOST = BR.NONE, BR.LEAST, BR.MOST
 PLACED, FIT_ERROR, SCORE_ERROR = BR.PLACED, BR.FIT_ERROR, BR.SCORE_ERROR
@@ -102,126 +100,10 @@ def per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, use
             state: State, pod_profile, counts=None, cnt=None):
     """balanced_ref.per_pod with the conjunct; `state` is updated in place. pod_profile None: no pod has a profile.
     Returns balanced_ref.per_pod's tuple."""
-    n, p = len(unsched), len(pod_digit)
-    alloc = np.asarray(alloc, np.int64).reshape(-1, n)
-    us = np.array(used, np.int64).reshape(-1, n)
-    req = np.asarray(req, np.int64).reshape(-1, p)
-    nres, G = alloc.shape[0], len(max_skew)
-    assert not w_balanced or nres >= 2
-    if mode != NONE or w_balanced:
-        assert max(alloc.max(initial=0), us.max(initial=0), req.max(initial=0)) <= BR.SCORE_MAX
-    if mode != NONE:
-        rw = np.asarray(rw, np.int64)
-        scored = [r for r in range(nres) if rw[r] > 0]
-        den = int(rw[scored].sum())
-        safe = np.where(alloc == 0, 1, alloc)
-    eff = np.asarray(eff, np.int64)
-    count = np.zeros(n, np.int64) if counts is None else np.array(counts, np.int64)
-    nd = np.asarray(node_digit, np.int64)
-    zn = np.full(n, -1, np.int64) if zone is None else np.asarray(zone, np.int64)
-    zs = np.unique(zn[zn >= 0])
-    zoned = zn >= 0
-    zsafe = np.where(zoned, zn, 0)
-    sk = np.asarray(max_skew, np.int64)
-    md = np.zeros(G, np.int64) if modes is None else np.asarray(modes, np.int64)
-    c = np.zeros((G, MAX_ZONES), np.int64) if cnt is None else np.array(cnt, np.int64).reshape(G, MAX_ZONES)
-    grp = np.full(p, -1, np.int64) if group is None else np.asarray(group, np.int64)
-    cls = np.full(p, -1, np.int64) if pod_class is None else np.asarray(pod_class, np.int64)
-    prf = np.full(p, -1, np.int64) if pod_profile is None else np.asarray(pod_profile, np.int64)
-    Q = len(state.match)
-    word = None if bits is None else np.asarray(bits, np.uint64)
-    Aq = np.zeros((max(n_classes, 1), n), np.int64) if A is None else np.asarray(A, np.int64).reshape(-1, n)
-    Tq = np.zeros((max(n_classes, 1), n), np.int64) if T is None else np.asarray(T, np.int64).reshape(-1, n)
-    blocked = np.asarray(unsched, bool) if "NodeUnschedulable" in plugins.filters else np.zeros(n, bool)
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    wt = np.array(SR.weights, np.float64)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    lowest = np.iinfo(np.int64).min
-    zeros = np.zeros(n, np.int64)
-    pz, rz, anyw = state.derived(zone)
-    for j in range(p):
-        pd = int(pod_digit[j])
-        g = int(grp[j]) if 0 <= grp[j] < G else -1
-        k = int(cls[j]) if 0 <= cls[j] < n_classes else -1
-        q = int(prf[j]) if 0 <= prf[j] < Q else -1
-        soft = g >= 0 and md[g] == SCHEDULE_ANYWAY
-        feas = count < eff
-        if not pod_tol[j]:
-            feas = feas & ~blocked
-        if k >= 0 and word is not None:
-            feas = feas & ((word >> np.uint64(k)) & np.uint64(1)).astype(bool)
-        for r in range(nres):
-            if req[r, j] > 0:
-                feas = feas & (alloc[r] - us[r] >= req[r, j])
-        if g >= 0 and not soft:
-            if len(zs) == 0:
-                feas = np.zeros(n, bool)
-            else:
-                feas = feas & zoned & (c[g][zsafe] - c[g][zs].min() < sk[g])   # the minimum over Zset, not narrowed
-        first = False
-        if q >= 0:
-            ok, first, AF = conjunct(state, q, zn, zoned, zsafe, pz, rz, anyw, feas)
-            feas = feas & ok
-        if not feas.any():
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):
-            status[j] = SCORE_ERROR
-            continue
-        total = np.zeros(n, np.int64)
-        raw = np.where((nd == pd) & (nd >= 0), 10, 0).astype(np.int64)
-        for w, nm in zip(plugins.weights, plugins.normalize):
-            total = total + RS._nn_scores(int(nm), raw, feas) * np.int64(O._wrap64(int(w)))
-        if mode != NONE:
-            acc = np.zeros(n, np.int64)
-            for r in scored:
-                qq = us[r] + req[r, j]
-                part = (alloc[r] - qq) if mode == LEAST else qq
-                none = (alloc[r] == 0) | (qq > alloc[r])
-                acc += np.where(none, 0, np.where(none, 0, part) * 100 // safe[r]) * rw[r]
-            total = total + (acc // den) * np.int64(int(weight))
-        ra = Aq[k] if k >= 0 else zeros
-        rt = Tq[k] if k >= 0 else zeros
-        max_a, max_t = int(ra[feas].max()), int(rt[feas].max())
-        na = zeros if max_a == 0 else ra * 100 // max_a
-        nt = zeros + 100 if max_t == 0 else 100 - rt * 100 // max_t
-        total = total + np.int64(int(w_aff)) * na + np.int64(int(w_taint)) * nt
-        if soft:
-            in_zs = np.zeros(MAX_ZONES, bool)
-            in_zs[zn[feas & zoned]] = True
-            size = int(in_zs.sum())
-            if size:
-                y = c[g].astype(np.float64) * wt[size]
-                y = y + np.float64(int(sk[g]) - 1)
-                r = np.rint(y)
-                r = r + ((y - np.floor(y) == 0.5) & (r < y))
-                rzz = r.astype(np.int64)
-                mx, mn = int(rzz[in_zs].max()), int(rzz[in_zs].min())
-                nz = np.full(MAX_ZONES, 100, np.int64) if mx == 0 else 100 * (mx + mn - rzz) // max(mx, 1)
-                total = total + np.int64(int(w_spread)) * np.where(zoned, nz[zsafe], 0)
-        if w_balanced:
-            total = total + np.int64(int(w_balanced)) * BR.bs_nodes(alloc, us, req[:, j])
-        sel = int(np.argmax(np.where(feas, total, lowest)))
-        idx[j], score[j] = sel, total[sel]
-        count[sel] += 1
-        us[:, sel] += req[:, j]
-        if g >= 0 and zn[sel] >= 0:
-            c[g, zn[sel]] += 1
-        if q >= 0:
-            M, AA = state.match[q], state.anti[q]
-            if first and AF and not ((state.present[sel] & state.HM) | (pz[zn[sel]] & state.ZM if zn[sel] >= 0 else 0)) & AF:
-                state.stats["first_pod"] += 1
-            state.present[sel] |= M
-            state.repel[sel] |= AA
-            if zn[sel] >= 0:
-                pz[zn[sel]] |= M
-                rz[zn[sel]] |= AA
-                anyw |= M & state.ZM
-            anyw |= M & state.HM
-    return idx, score, status, count.astype(np.int32), us, c.astype(np.int32)
+    import seq_ref
+    return seq_ref.per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
+                           max_skew, mode, weight, rw, bits, n_classes, pod_class, A, T, w_aff, w_taint, modes, w_spread,
+                           w_balanced, state, pod_profile, counts=counts, cnt=cnt)
 
 
 def gen_case(seed: int, n: int, p: int, nres: int, T: int, n_zones: int = 6) -> dict:

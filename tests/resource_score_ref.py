@@ -2,12 +2,14 @@
 scoring": msh_set_resource_score with LEAST_ALLOCATED / MOST_ALLOCATED). Neither is the code under test; test
 infrastructure only.
 
-1. `serial`: the literal loop. Per pod the feasible list as resource_fit_ref.serial builds it, per feasible node
-   the total from the header's formulas in Python ints (NodeNumber through oracle.normalize over the feasible list,
-   plus weight x RS), the first maximum, the commit. Tiny shapes.
-2. `per_pod`: written separately, in numpy int64: a feasibility mask, NodeNumber's normalizers spelled out on
-   arrays, RS for every node at once, one argmax per pod. Mid sizes.
-tests/test_resource_score.py checks the two against each other and mode NONE against resource_fit_ref.serial.
+The contract, per pod in order: the feasible list is resource_fit_ref.serial's; a feasible node's total is the
+header's formula (NodeNumber normalized over the feasible list, plus weight x RS with q = used + req before the
+commit); the first maximum in List order wins; the commit is resource_fit_ref's. Mode NONE leaves NodeNumber alone.
+
+`serial` (Python ints, tiny shapes) and `per_pod` (numpy int64, mid sizes) are seq_ref's two loops with every later
+feature left absent; `resource_score` and `_nn_scores` are the helpers those loops use, the first in `serial` only and
+the second (NodeNumber's normalizers spelled out on arrays) in `per_pod` only. tests/test_resource_score.py checks the
+two against each other and mode NONE against resource_fit_ref.serial, which shares no code with them.
 
 Modes: NONE = 0, LEAST = 1, MOST = 2 (msh_resource_score). `rw`: one weight per resource, 0 = not scored.
 """
@@ -41,48 +43,9 @@ def resource_score(mode, c, q, rw):
 
 def serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, mode, weight, rw, counts=None):
     """(idx, score, status, counts after, used after); alloc / used shaped (nres, n), req (nres, p)."""
-    if mode == NONE:
-        return R.serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, counts)
-    n, p = len(unsched), len(pod_digit)
-    assert n * p <= 2 * 10**5, "the serial loop is for tiny shapes"
-    nres = len(alloc)
-    eff = [int(x) for x in eff]
-    cnt = [0] * n if counts is None else [int(x) for x in counts]
-    al = [[int(x) for x in row] for row in alloc]
-    us = [[int(x) for x in row] for row in used]
-    rw = [int(x) for x in rw]
-    has_nu = "NodeUnschedulable" in plugins.filters
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    for j in range(p):
-        pd, tol = int(pod_digit[j]), bool(pod_tol[j])
-        rq = [int(req[r][j]) for r in range(nres)]
-        feas = [i for i in range(n)
-                if (not has_nu or not unsched[i] or tol) and cnt[i] < eff[i]
-                and all(rq[r] <= al[r][i] - us[r][i] for r in range(nres) if rq[r] > 0)]
-        if not feas:
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):
-            status[j] = SCORE_ERROR
-            continue
-        total = [0] * len(feas)
-        for w, nm in zip(plugins.weights, plugins.normalize):
-            raw = [10 if 0 <= int(node_digit[i]) == pd else 0 for i in feas]
-            total = [O._wrap64(t + s * int(w)) for t, s in zip(total, O.normalize(int(nm), raw))]
-        for k, i in enumerate(feas):
-            rs = resource_score(mode, [al[r][i] for r in range(nres)], [us[r][i] + rq[r] for r in range(nres)], rw)
-            total[k] = O._wrap64(total[k] + int(weight) * rs)
-        best = max(total)
-        sel = feas[total.index(best)]  # the first maximum in List order
-        idx[j], score[j] = sel, best
-        cnt[sel] += 1
-        for r in range(nres):
-            us[r][sel] += rq[r]
-    return idx, score, status, np.array(cnt, np.int32), np.array(us, np.int64).reshape(nres, n)
+    import seq_ref
+    return seq_ref.serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, mode=mode,
+                          weight=weight, rw=rw, counts=counts)[:5]
 
 
 def _nn_scores(nm, raw, feas):
@@ -102,57 +65,9 @@ def _nn_scores(nm, raw, feas):
 
 def per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, mode, weight, rw, counts=None):
     """(idx, score, status, counts after, used after): per pod one numpy pass over the nodes, int64 throughout."""
-    if mode == NONE:
-        return R.per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, counts)
-    n, p = len(unsched), len(pod_digit)
-    alloc = np.asarray(alloc, np.int64)
-    us = np.array(used, np.int64)
-    req = np.asarray(req, np.int64)
-    assert max(alloc.max(initial=0), us.max(initial=0), req.max(initial=0)) <= SCORE_MAX, "int64 would overflow"
-    nres = alloc.shape[0]
-    rw = np.asarray(rw, np.int64)
-    scored = [r for r in range(nres) if rw[r] > 0]
-    den = int(rw[scored].sum())
-    eff = np.asarray(eff, np.int64)
-    cnt = np.zeros(n, np.int64) if counts is None else np.array(counts, np.int64)
-    nd = np.asarray(node_digit, np.int64)
-    open_nt = ~np.asarray(unsched, bool) if "NodeUnschedulable" in plugins.filters else np.ones(n, bool)
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    safe = np.where(alloc == 0, 1, alloc)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    lowest = np.iinfo(np.int64).min
-    for j in range(p):
-        pd = int(pod_digit[j])
-        feas = (cnt < eff) if pod_tol[j] else (open_nt & (cnt < eff))
-        for r in range(nres):
-            if req[r, j] > 0:
-                feas = feas & (req[r, j] <= alloc[r] - us[r])
-        if not feas.any():
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):
-            status[j] = SCORE_ERROR
-            continue
-        total = np.zeros(n, np.int64)
-        raw = np.where((nd == pd) & (nd >= 0), 10, 0).astype(np.int64)
-        for w, nm in zip(plugins.weights, plugins.normalize):
-            total = total + _nn_scores(int(nm), raw, feas) * int(w)
-        acc = np.zeros(n, np.int64)
-        for r in scored:
-            q = us[r] + req[r, j]
-            part = (alloc[r] - q) if mode == LEAST else q
-            none = (alloc[r] == 0) | (q > alloc[r])
-            s = np.where(none, 0, np.where(none, 0, part) * 100 // safe[r])
-            acc += s * rw[r]
-        total = total + (acc // den) * int(weight)
-        sel = int(np.argmax(np.where(feas, total, lowest)))  # argmax returns the first maximum
-        idx[j], score[j] = sel, total[sel]
-        cnt[sel] += 1
-        us[:, sel] += req[:, j]
-    return idx, score, status, cnt.astype(np.int32), us
+    import seq_ref
+    return seq_ref.per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, mode=mode,
+                           weight=weight, rw=rw, counts=counts)[:5]
 
 
 def sweep_case(O, rng, case, sizes):

@@ -7,11 +7,11 @@ zone[i] >= 0 and cnt[g][zone[i]] + 1 - min over z in Zset of cnt[g][z] <= max_sk
 on at least one node. Status, NodeNumber totals in every normalize mode, the first maximum and the commit are the
 resource-fit form's; a PLACED grouped pod also adds 1 to cnt[g][zone[sel]].
 
-1. `serial`: a plain Python loop that looks at every (pod, node) pair and reads cnt[g][zone[i]] for every node.
-   For tiny shapes (p * n <= 2 * 10^5).
-2. `per_pod`: one pod at a time with the nodes in numpy (the skew of every node gathered from the cnt array); the
-   totals of the two NodeNumber classes come from oracle.normalize over the raw scores present, as in
-   resource_fit_ref.per_pod. tests/test_spread.py shows it equal to `serial` before anything relies on it.
+`serial` (a plain Python loop that reads cnt[g][zone[i]] for every node, for tiny shapes: p * n <= 2 * 10^5) and
+`per_pod` (one pod at a time with the nodes in numpy, the skew of every node gathered from the cnt array) are
+seq_ref's two loops with no score beyond NodeNumber and every later feature left absent. tests/test_spread.py shows
+`per_pod` equal to `serial`, and both equal to resource_fit_ref and node_capacity_ref on ungrouped pods, before
+anything relies on them.
 
 Neither forms a per-zone "allowed" set: each node's verdict is computed from the cnt array directly. alloc / used
 are shaped (nres, n) and req (nres, p), with nres = 0 for a call without requests. `gen_case` is the seeded
@@ -48,133 +48,17 @@ def clean_groups(group, G: int) -> np.ndarray:
 def serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group, max_skew,
            counts=None, cnt=None):
     """(idx, score, status, counts after, used after, cnt after); cnt shaped (G, MAX_ZONES)."""
-    n, p = len(unsched), len(pod_digit)
-    assert n * p <= 2 * 10**5, "the serial loop is for tiny shapes"
-    nres, G = len(alloc), len(max_skew)
-    eff = [int(x) for x in eff]
-    count = [0] * n if counts is None else [int(x) for x in counts]
-    al = [[int(x) for x in row] for row in alloc]
-    us = [[int(x) for x in row] for row in used]
-    zn = [int(z) for z in zone]
-    zs = zset(zone)
-    sk = [int(x) for x in max_skew]
-    c = [[0] * MAX_ZONES for _ in range(G)] if cnt is None else [[int(x) for x in row] for row in cnt]
-    grp = clean_groups(group, G)
-    has_nu = "NodeUnschedulable" in plugins.filters
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    for j in range(p):
-        pd, tol, g = int(pod_digit[j]), bool(pod_tol[j]), int(grp[j])
-        rq = [int(req[r][j]) for r in range(nres)]
-        feas = []
-        for i in range(n):
-            if has_nu and unsched[i] and not tol:
-                continue
-            if not count[i] < eff[i]:
-                continue
-            if not all(rq[r] <= al[r][i] - us[r][i] for r in range(nres) if rq[r] > 0):
-                continue
-            if g >= 0:
-                if zn[i] < 0:
-                    continue
-                if c[g][zn[i]] + 1 - min(c[g][z] for z in zs) > sk[g]:
-                    continue
-            feas.append(i)
-        if not feas:
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):  # NodeNumber.Score finds no PreScore state
-            status[j] = SCORE_ERROR
-            continue
-        total = [0] * len(feas)
-        for w, mode in zip(plugins.weights, plugins.normalize):
-            raw = [10 if 0 <= int(node_digit[i]) == pd else 0 for i in feas]
-            total = [O._wrap64(t + s * int(w)) for t, s in zip(total, O.normalize(int(mode), raw))]
-        best = max(total)
-        sel = feas[total.index(best)]  # the first maximum in List order
-        idx[j], score[j] = sel, best
-        count[sel] += 1
-        for r in range(nres):
-            us[r][sel] += rq[r]
-        if g >= 0:
-            c[g][zn[sel]] += 1
-    return (idx, score, status, np.array(count, np.int32), np.array(us, np.int64).reshape(nres, n),
-            np.array(c, np.int32).reshape(G, MAX_ZONES))
+    import seq_ref
+    return seq_ref.serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
+                          max_skew, counts=counts, cnt=cnt)
 
 
 def per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group, max_skew,
             counts=None, cnt=None):
     """(idx, score, status, counts after, used after, cnt after): per pod one numpy pass over the nodes."""
-    n, p = len(unsched), len(pod_digit)
-    alloc = np.asarray(alloc, np.int64).reshape(-1, n)
-    us = np.array(used, np.int64).reshape(-1, n)
-    req = np.asarray(req, np.int64).reshape(-1, p)
-    nres, G = alloc.shape[0], len(max_skew)
-    eff = np.asarray(eff, np.int64)
-    count = np.zeros(n, np.int64) if counts is None else np.array(counts, np.int64)
-    nd = np.asarray(node_digit, np.int64)
-    zn = np.asarray(zone, np.int64)
-    zoned = zn >= 0
-    zsafe = np.where(zoned, zn, 0)
-    zs = np.array(zset(zone), np.int64)
-    sk = np.asarray(max_skew, np.int64)
-    c = np.zeros((G, MAX_ZONES), np.int64) if cnt is None else np.array(cnt, np.int64).reshape(G, MAX_ZONES)
-    grp = clean_groups(group, G)
-    has_nu = "NodeUnschedulable" in plugins.filters
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    open_all = np.ones(n, bool)
-    open_nt = ~np.asarray(unsched, bool) if has_nu else open_all
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-
-    def class_totals(raws):  # totals of the raw scores present among the feasible nodes, by raw score
-        total = {r: 0 for r in raws}
-        for w, mode in zip(plugins.weights, plugins.normalize):
-            for r, s in zip(raws, O.normalize(int(mode), list(raws))):
-                total[r] = O._wrap64(total[r] + s * int(w))
-        return total
-
-    for j in range(p):
-        pd, g = int(pod_digit[j]), int(grp[j])
-        feas = (open_all if pod_tol[j] else open_nt) & (count < eff)
-        for r in range(nres):
-            if req[r, j] > 0:
-                feas = feas & (req[r, j] <= alloc[r] - us[r])
-        if g >= 0:
-            if len(zs) == 0:
-                feas = np.zeros(n, bool)
-            else:
-                feas = feas & zoned & (c[g][zsafe] + 1 - c[g][zs].min() <= sk[g])
-        if not feas.any():
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):
-            status[j] = SCORE_ERROR
-            continue
-        match = feas & (nd == pd) & (nd >= 0)
-        other = feas & ~match
-        fm = int(np.argmax(match)) if match.any() else -1
-        fx = int(np.argmax(other)) if other.any() else -1
-        raws = ([10] if fm >= 0 else []) + ([0] if fx >= 0 else [])
-        total = class_totals(raws)
-        if fm >= 0 and fx >= 0:
-            if total[10] == total[0]:
-                sel, best = min(fm, fx), total[10]
-            else:
-                sel, best = (fm, total[10]) if total[10] > total[0] else (fx, total[0])
-        else:
-            sel, best = (fm, total[10]) if fm >= 0 else (fx, total[0])
-        idx[j], score[j] = sel, best
-        count[sel] += 1
-        us[:, sel] += req[:, j]
-        if g >= 0:
-            c[g, zn[sel]] += 1
-    return idx, score, status, count.astype(np.int32), us, c.astype(np.int32)
+    import seq_ref
+    return seq_ref.per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
+                           max_skew, counts=counts, cnt=cnt)
 
 
 def gen_case(seed: int, max_n: int = 2048, max_p: int = 2000) -> dict:

@@ -9,8 +9,8 @@ and cnt[g][zone[i]] + 1 - min over Zset of cnt[g] <= max_skew[g]); a feasible no
 goes to the first maximum in List order; a PLACED pod adds 1 to count[sel], its requests to used[:, sel] and, for
 g >= 0, 1 to cnt[g][zone[sel]].
 
-1. `serial`: a plain Python loop over every (pod, node) pair, Python ints, the header's formulas. Tiny shapes.
-2. `per_pod`: written separately, one pod at a time with the nodes in numpy int64.
+`serial` (Python ints, the header's formulas, tiny shapes) and `per_pod` (one pod at a time with the nodes in numpy
+int64) are seq_ref's two loops with every later feature left absent.
 Neither forms a per-zone "allowed" set or packs (score, node) into a key: a node's verdict is computed from the cnt
 array directly, and the selection is a plain first maximum over the feasible nodes' totals.
 
@@ -35,65 +35,9 @@ def serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used
     if mode == NONE:
         return S.serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
                         max_skew, counts, cnt)
-    n, p = len(unsched), len(pod_digit)
-    assert n * p <= 2 * 10**5, "the serial loop is for tiny shapes"
-    nres, G = len(alloc), len(max_skew)
-    eff = [int(x) for x in eff]
-    count = [0] * n if counts is None else [int(x) for x in counts]
-    al = [[int(x) for x in row] for row in alloc]
-    us = [[int(x) for x in row] for row in used]
-    rw = [int(x) for x in rw]
-    zn = [int(z) for z in zone]
-    zs = S.zset(zone)
-    sk = [int(x) for x in max_skew]
-    c = [[0] * MAX_ZONES for _ in range(G)] if cnt is None else [[int(x) for x in row] for row in cnt]
-    grp = S.clean_groups(group, G)
-    has_nu = "NodeUnschedulable" in plugins.filters
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    for j in range(p):
-        pd, tol, g = int(pod_digit[j]), bool(pod_tol[j]), int(grp[j])
-        rq = [int(req[r][j]) for r in range(nres)]
-        feas = []
-        for i in range(n):
-            if has_nu and unsched[i] and not tol:
-                continue
-            if not count[i] < eff[i]:
-                continue
-            if not all(rq[r] <= al[r][i] - us[r][i] for r in range(nres) if rq[r] > 0):
-                continue
-            if g >= 0:
-                if zn[i] < 0:
-                    continue
-                if c[g][zn[i]] + 1 - min(c[g][z] for z in zs) > sk[g]:
-                    continue
-            feas.append(i)
-        if not feas:
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):  # NodeNumber.Score finds no PreScore state
-            status[j] = SCORE_ERROR
-            continue
-        total = [0] * len(feas)
-        for w, nm in zip(plugins.weights, plugins.normalize):
-            raw = [10 if 0 <= int(node_digit[i]) == pd else 0 for i in feas]
-            total = [O._wrap64(t + s * int(w)) for t, s in zip(total, O.normalize(int(nm), raw))]
-        for k, i in enumerate(feas):
-            rs = RS.resource_score(mode, [al[r][i] for r in range(nres)], [us[r][i] + rq[r] for r in range(nres)], rw)
-            total[k] = O._wrap64(total[k] + int(weight) * rs)
-        best = max(total)
-        sel = feas[total.index(best)]  # the first maximum in List order
-        idx[j], score[j] = sel, best
-        count[sel] += 1
-        for r in range(nres):
-            us[r][sel] += rq[r]
-        if g >= 0:
-            c[g][zn[sel]] += 1
-    return (idx, score, status, np.array(count, np.int32), np.array(us, np.int64).reshape(nres, n),
-            np.array(c, np.int32).reshape(G, MAX_ZONES))
+    import seq_ref
+    return seq_ref.serial(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
+                          max_skew, mode, weight, rw, counts=counts, cnt=cnt)
 
 
 def per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group, max_skew,
@@ -101,69 +45,9 @@ def per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, use
     if mode == NONE:
         return S.per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
                          max_skew, counts, cnt)
-    n, p = len(unsched), len(pod_digit)
-    alloc = np.asarray(alloc, np.int64).reshape(-1, n)
-    us = np.array(used, np.int64).reshape(-1, n)
-    req = np.asarray(req, np.int64).reshape(-1, p)
-    assert max(alloc.max(initial=0), us.max(initial=0), req.max(initial=0)) <= RS.SCORE_MAX, "int64 would overflow"
-    nres, G = alloc.shape[0], len(max_skew)
-    rw = np.asarray(rw, np.int64)
-    scored = [r for r in range(nres) if rw[r] > 0]
-    den = int(rw[scored].sum())
-    eff = np.asarray(eff, np.int64)
-    count = np.zeros(n, np.int64) if counts is None else np.array(counts, np.int64)
-    nd = np.asarray(node_digit, np.int64)
-    zn = np.asarray(zone, np.int64)
-    in_zone = [zn == z for z in range(MAX_ZONES)]  # per zone id, the nodes of that zone
-    zs = S.zset(zone)
-    sk = np.asarray(max_skew, np.int64)
-    c = np.zeros((G, MAX_ZONES), np.int64) if cnt is None else np.array(cnt, np.int64).reshape(G, MAX_ZONES)
-    grp = S.clean_groups(group, G)
-    open_nt = ~np.asarray(unsched, bool) if "NodeUnschedulable" in plugins.filters else np.ones(n, bool)
-    nn_pre = "NodeNumber" in plugins.prescore
-    assert all(s == "NodeNumber" for s in plugins.score)
-    safe = np.where(alloc == 0, 1, alloc)
-    idx = np.full(p, -1, np.int32)
-    score = np.zeros(p, np.int64)
-    status = np.zeros(p, np.int32)
-    lowest = np.iinfo(np.int64).min
-    for j in range(p):
-        pd, g = int(pod_digit[j]), int(grp[j])
-        feas = (count < eff) if pod_tol[j] else (open_nt & (count < eff))
-        for r in range(nres):
-            if req[r, j] > 0:
-                feas = feas & (req[r, j] <= alloc[r] - us[r])
-        if g >= 0:
-            # a node's skew after taking the pod, from its zone's count; a node without a zone never qualifies
-            after = np.full(n, np.iinfo(np.int64).max)
-            low = min((int(c[g, z]) for z in zs), default=0)
-            for z in zs:
-                after[in_zone[z]] = int(c[g, z]) + 1 - low
-            feas = feas & (after <= sk[g])
-        if not feas.any():
-            status[j] = FIT_ERROR
-            continue
-        if plugins.score and not (nn_pre and 0 <= pd <= 9):
-            status[j] = SCORE_ERROR
-            continue
-        total = np.zeros(n, np.int64)
-        raw = np.where((nd == pd) & (nd >= 0), 10, 0).astype(np.int64)
-        for w, nm in zip(plugins.weights, plugins.normalize):
-            total = total + RS._nn_scores(int(nm), raw, feas) * int(w)
-        acc = np.zeros(n, np.int64)
-        for r in scored:
-            q = us[r] + req[r, j]
-            part = (alloc[r] - q) if mode == LEAST else q
-            none = (alloc[r] == 0) | (q > alloc[r])
-            acc += np.where(none, 0, np.where(none, 0, part) * 100 // safe[r]) * rw[r]
-        total = total + (acc // den) * int(weight)
-        sel = int(np.argmax(np.where(feas, total, lowest)))  # argmax returns the first maximum
-        idx[j], score[j] = sel, total[sel]
-        count[sel] += 1
-        us[:, sel] += req[:, j]
-        if g >= 0:
-            c[g, zn[sel]] += 1
-    return idx, score, status, count.astype(np.int32), us, c.astype(np.int32)
+    import seq_ref
+    return seq_ref.per_pod(O, unsched, node_digit, pod_digit, pod_tol, plugins, eff, alloc, used, req, zone, group,
+                           max_skew, mode, weight, rw, counts=counts, cnt=cnt)
 
 
 def gen_case(seed: int, max_n: int = 2048, max_p: int = 2000) -> dict:
