@@ -140,6 +140,9 @@ typedef struct msh_options {
   int32_t seq_pod_waves; /* 0 auto | 1, 2, 4, 8 waves sharing a 64-pod block (one scanning wave, no capacity) */
   int32_t gen_keys;     /* 0 auto (64-bit totals below 2^53 as double keys) | 1 uint64 keys */
   int32_t gen_nnkey;    /* 0 auto (compare-free NodeNumber key) | 1 compare + select */
+  int32_t pair_fold;    /* 0 auto (LDS form, NONE / DEFAULT, 4-wave workgroups: non-tolerating pods of digits 0-7
+                         * first, their blocks scanned with X | D3 from the scalar unit) | 1 off: every block
+                         * takes the general chain, in launch order */
 } msh_options;
 int msh_create_ex(int device, const msh_options* opts, msh_ctx** out_ctx);
 

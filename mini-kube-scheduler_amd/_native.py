@@ -132,7 +132,7 @@ class Options(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("batch_kernel", C.c_int32), ("pair_planes", C.c_int32),
                 ("pair_noax", C.c_int32), ("pair_slices", C.c_int32), ("seq_waves", C.c_int32),
                 ("seq_split", C.c_int32), ("seq_pod_waves", C.c_int32), ("gen_keys", C.c_int32),
-                ("gen_nnkey", C.c_int32)]
+                ("gen_nnkey", C.c_int32), ("pair_fold", C.c_int32)]
 
 
 # Named values of the msh_options fields (an int passes through unchanged, for the library to check).
@@ -146,6 +146,7 @@ OPTION_NAMES = {
     "seq_pod_waves": {"auto": 0},
     "gen_keys": {"auto": 0, "f53": 0, "u64": 1},
     "gen_nnkey": {"auto": 0, "select": 1},
+    "pair_fold": {"auto": 0, "on": 0, "off": 1},
 }
 
 

@@ -734,7 +734,8 @@ bool apply_options(const msh_options& o, msh::DeviceInfo& d, std::string* err) {
       !in("pair_noax", o.pair_noax, {0, 1, 2}) || !in("pair_slices", o.pair_slices, {0, 1, 2, 4}) ||
       !in("seq_waves", o.seq_waves, {0, 1, 4, 15, 16}) || !in("seq_split", o.seq_split, {0, 1, 2}) ||
       !in("seq_pod_waves", o.seq_pod_waves, {0, 1, 2, 4, 8}) ||
-      !in("gen_keys", o.gen_keys, {0, 1}) || !in("gen_nnkey", o.gen_nnkey, {0, 1}))
+      !in("gen_keys", o.gen_keys, {0, 1}) || !in("gen_nnkey", o.gen_nnkey, {0, 1}) ||
+      !in("pair_fold", o.pair_fold, {0, 1}))
     return false;
   d.batch_kernel = o.batch_kernel;
   d.pair_planes = o.pair_planes;
@@ -745,6 +746,7 @@ bool apply_options(const msh_options& o, msh::DeviceInfo& d, std::string* err) {
   d.seq_pod_waves = o.seq_pod_waves;
   d.gen_f53 = o.gen_keys == 0 ? 1 : 0;
   d.gen_nnkey = o.gen_nnkey == 0 ? 1 : 0;
+  d.pair_fold = o.pair_fold == 0 ? 1 : 0;
   return true;
 }
 

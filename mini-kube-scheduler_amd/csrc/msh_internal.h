@@ -52,6 +52,11 @@ struct DeviceInfo {
   // reduction in the LDS form (the first feasible node comes from the scalar unit): the option is still
   // accepted and has no effect on them
   int pair_noax = -1;
+  // msh_options.pair_fold: the identity-like modes' LDS-staged form in 4-wave workgroups moves a
+  // workgroup's class-0 pods (not tolerating, code bit 3 clear) to its first blocks and scans the blocks
+  // of class 0 only with X | D3 built on the scalar unit (1, the default: 65.7-68.0 against 71.4-73.2 us
+  // per 32-batch C3 launch), or scans every block with the general chain in launch order (0): DESIGN.md §4.2
+  int pair_fold = 1;
   // msh_options.seq_split, without a capacity: the per-pair batch kernel with the commit epilogue (auto,
   // 2), the sequential kernel's 64-pod blocks of consecutive pods, one workgroup each (1), or the whole
   // batch in one workgroup, in order (serial, 0)
@@ -124,6 +129,7 @@ struct BatchDesc {
   int32_t n_pods;
   int32_t reserved;
 };
+constexpr int32_t PAIR_FLAG_FOLD = 2;  // PairCommon::noax, identity-like modes: DeviceInfo::pair_fold
 constexpr int MULTI_MAX = 32;  // batches per launch (kernel-argument descriptors, 40 B each: ~1.3 KB)
 
 // The per-pair kernel (pair_kernel): nb (1..MULTI_MAX) batches in one launch, or (shard) the
@@ -133,7 +139,8 @@ struct PairCommon {
   int32_t n_groups;
   int32_t g_full;          // groups [0, g_full) hold real nodes only (no padding slot)
   int32_t gps;             // groups per slice wave (set by the launcher)
-  int32_t noax;            // pair_lds_kernel: group 0 may settle the non-match reduction (launcher)
+  int32_t noax;            // pair_lds_kernel: group 0 may settle the non-match reduction (launcher); the
+                           // identity-like instances read PAIR_FLAG_FOLD of it and nothing else
   int32_t nb;
   PluginParams pp;
   int64_t node_base;       // shard mode: global index of local node 0

@@ -366,8 +366,9 @@ __global__ __launch_bounds__(PAIR_WAVES * WAVE) void pair_kernel(PairArgsN<NB> a
 // and a lane selects one. Group 0's first match comes from dm' alone there (group_firsts_lds).
 // The forms that lost their A/B (profiles/r4_ab_pair_planes.txt) are no longer built:
 // one, three and four blocks per wave; the pure-LDS full-group form (a full group always takes hybrid
-// planes: X and D3 by scalar loads, D0-D2 from LDS); compaction in the identity-like modes and hybrid
-// form 1 in REVERSE / MINMAX. What is left per (SHARD, KX) is the launcher's choice at 4 and 16 waves.
+// planes: X and D3 by scalar loads, D0-D2 from LDS); tolerates-only compaction in the identity-like modes
+// (they sort by class 0 instead, see pair_group_fold) and hybrid form 1 in REVERSE / MINMAX. What is
+// left per (SHARD, KX) is the launcher's choice at 4 and 16 waves.
 // ---------------------------------------------------------------------------------------
 constexpr int PL_WAVES = 4;  // waves per workgroup (tables up to PAIR_LDS_MAX_GROUPS groups)
 constexpr int PL_WAVES_BIG = 16;  // waves per workgroup for larger tables: one copy of up to 78 KB serves
@@ -493,6 +494,33 @@ __device__ __forceinline__ void pair_group_hy(const uint32_t (&pl)[PLANE_N][PLAN
   }
 }
 
+// The identity-like modes' group for a block of class 0: none of its 64 pods tolerates the taint
+// (nT = all-ones) and none has code bit 3 (P3 = 0: digits 0-7). The term (X & nT) | (D3 ^ P3) of dm' is
+// then X | D3, the same word for every lane, and X and D3 already sit in SGPRs (hybrid planes), so the
+// wave builds it once per group on the scalar unit (fold_planes: plain C++ on wave-uniform values, four
+// 64-bit ORs per group, shared by the wave's blocks) and the lane's chain is three v_bitop3 per word,
+// one with an SGPR operand, instead of five with two: 3.5 VALU per word with the AND3 into the flag,
+// against 5.5. dm' is the same word bit for bit. A padding slot (node code 15, X = 0) still sets its
+// dm' bit, through D3 (code 7 differs from 15 in D3 only).
+typedef uint64_t u64x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x8 fold_planes(const u32x8& X, const u32x8& D3) {
+  return __builtin_bit_cast(u32x8, __builtin_bit_cast(u64x4, X) | __builtin_bit_cast(u64x4, D3));
+}
+__device__ __forceinline__ void pair_group_fold(const uint32_t (&pl)[PLANE_N][PLANE_GW], const u32x8& S, uint32_t P0,
+                                                uint32_t P1, uint32_t P2, uint32_t& am) {
+#pragma unroll
+  for (int w = 0; w < PLANE_GW; w += 2) {
+    uint32_t t[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      uint32_t u = bop3_or_xor(S[w + h], pl[0][w + h], P0);
+      u = bop3_or_xor(u, pl[1][w + h], P1);
+      t[h] = bop3_or_xor(u, pl[2][w + h], P2);
+    }
+    am = bop3_and3(am, t[0], t[1]);
+  }
+}
+
 // The lane's first feasible match (KIND 0) or feasible non-match (1) in group g of the LDS table,
 // NOFIT if none: half a group (four words, 6 x 4 plane words live) at a time.
 template <int KIND>
@@ -606,14 +634,24 @@ __device__ __forceinline__ void group_firsts_lds(const uint4* __restrict__ s_tab
 // (amdgpu_waves_per_eu(8): 64 VGPRs, 36 B of spills outside the scan loop, against the 78 VGPRs and 6 waves
 // it had then) ran 78.1 against 78.0 at w=3 DEFAULT and 78.6 against 78.2 at w=1 NONE. Today's identity-like
 // instances take 56 VGPRs, 8 waves per SIMD, without the attribute: profiles/pair_one_flag_regs.json.)
+// The identity-like modes in 4-wave workgroups (FOLD, msh_options.pair_fold) move the workgroup's class-0
+// pods (not tolerating, code bit 3 clear) to its first blocks and scan a block of class 0 only with
+// S = X | D3 built on the scalar unit: 3.5 VALU per word, one SGPR operand, against 5.5 with two
+// (pair_group_fold). One scan loop per subset of the wave's two blocks, chosen once per wave: the
+// scalar unit is not idle (a form that built S for all four classes inside one loop, with a branch
+// per block and group, added 765 SALU per wave and ran 82 against 70 us). 60 VGPRs,
+// 8 waves per SIMD, 2,080 B of static LDS (profiles/pair_fold_regs.json). The 16-wave instances keep
+// the general chain (the sort's static LDS on top of a table of up to 78 KB, as for KX above; not measured).
 template <bool SHARD, bool KX, int W>
 __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
   constexpr bool CMP = KX && W == PL_WAVES;
+  constexpr bool FOLD = !KX && W == PL_WAVES;  // the identity-like modes' class-0 partition and folded scan
   constexpr int HY = KX ? 2 : 1;
   extern __shared__ uint4 s_tab[];  // n_groups * GROUP_DWORDS / 4
   constexpr int NSL = W * PL_BPW;   // 64-pod slices of the workgroup
-  __shared__ uint32_t s_cnt[CMP ? NSL : 1];
-  __shared__ uint32_t s_pod[CMP ? NSL * WAVE : 1];
+  __shared__ uint32_t s_cnt[(CMP || FOLD) ? NSL : 1];
+  __shared__ uint32_t s_pod[(CMP || FOLD) ? NSL * WAVE : 1];
+  const bool fold = FOLD && (a.noax & PAIR_FLAG_FOLD) != 0;  // launch-uniform (msh_options.pair_fold)
   const BatchDesc& d = a.d[blockIdx.y];
   const int32_t np = d.n_pods;
   const int32_t wg0 = (int32_t)blockIdx.x * NSL * WAVE;  // first pod of this workgroup
@@ -675,12 +713,49 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
     __syncthreads();
 #pragma unroll
     for (int b = 0; b < PL_BPW; ++b) pk[b] = s_pod[(wv * PL_BPW + b) * WAVE + lane];
+  } else if constexpr (FOLD) {
+    if (fold) {
+      // FOLD: a stable partition of the workgroup's 512 pods through LDS, class 0 (not tolerating, code bit
+      // 3 clear: three pods in four) first, every other pod (padding lanes, code 14, among them) after it
+      // in launch order. All blocks but the one that straddles the boundary then hold class 0 only or
+      // none of it, and the former take the folded scan (pair_group_fold).
+      uint64_t m0[PL_BPW];  // per block: the lanes of class 0
+#pragma unroll
+      for (int b = 0; b < PL_BPW; ++b) {
+        m0[b] = __ballot((pk[b] & 0x18u) == 0u);
+        if (lane == 0) s_cnt[wv * PL_BPW + b] = (uint32_t)__builtin_popcountll(m0[b]);
+      }
+      __syncthreads();
+      uint32_t tot = 0, pre[PL_BPW];
+#pragma unroll
+      for (int k = 0; k < NSL; ++k) {
+        const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_cnt[k]);
+#pragma unroll
+        for (int b = 0; b < PL_BPW; ++b)
+          if (k == wv * PL_BPW + b) pre[b] = tot;
+        tot += c;
+      }
+#pragma unroll
+      for (int b = 0; b < PL_BPW; ++b) {
+        const uint32_t sl = (uint32_t)(wv * PL_BPW + b);
+        const bool c0 = (pk[b] & 0x18u) == 0u;
+        const uint64_t mk = c0 ? m0[b] : ~m0[b];
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+        s_pod[(c0 ? pre[b] : tot + (sl * WAVE - pre[b])) + below] = pk[b];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int b = 0; b < PL_BPW; ++b) pk[b] = s_pod[(wv * PL_BPW + b) * WAVE + lane];
+    } else {
+      __syncthreads();
+    }
   } else {
     __syncthreads();
   }
   uint32_t P0[PL_BPW], P1[PL_BPW], P2[PL_BPW], P3[PL_BPW], nT[PL_BPW], code[PL_BPW];
   int32_t jj[PL_BPW];
   int ty[PL_BPW];  // wave-uniform per block: 0 no pod tolerates, 1 every pod does, 2 mixed
+  bool pure[PL_BPW];  // FOLD, wave-uniform per block: every pod of the block is of class 0 (two ballots)
   bool any_act = false;
 #pragma unroll
   for (int b = 0; b < PL_BPW; ++b) {
@@ -694,6 +769,8 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
     nT[b] = t ? 0u : 0xFFFFFFFFu;
     const uint64_t tm = __ballot(t != 0u);
     ty[b] = CMP ? (tm == 0 ? 0 : (~tm == 0 ? 1 : 2)) : 2;
+    const uint64_t pm = FOLD ? __ballot((c >> 3) != 0u) : 0;
+    pure[b] = fold && tm == 0 && pm == 0;
     any_act = any_act || __ballot(jj[b] < np) != 0;
   }
   if (!any_act) return;  // wave-uniform; no barrier below
@@ -733,8 +810,9 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
 #pragma unroll
     for (int b = 0; b < PL_BPW; ++b) group_firsts_lds<KX>(s_tab, 0u, P0[b], P1[b], P2[b], P3[b], nT[b], code[b] != CODE_NONE_POD, rm[b], rx[b]);
   };
-  auto scan = [&](auto noax) {
+  auto scan = [&](auto noax, auto fsel) {  // fsel: bit b set = block b is of class 0 (FOLD; wave-uniform)
     constexpr bool NOAX = decltype(noax)::value;
+    constexpr int FSEL = decltype(fsel)::value;
     constexpr bool KXS = KX && !NOAX;  // the non-match flags are tracked
     for (int32_t g = n_groups - 1; g > 0; g -= 2) {
       uint32_t ams[PL_BPW], ax[PL_BPW];
@@ -769,6 +847,14 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
                          : "s"(a.planes + (size_t)gg * GROUP_DWORDS), "n"(PLANE_X * PLANE_GW * 4), "n"(3 * PLANE_GW * 4));
           }
           lds_group<3>(pl, s_tab, gg);
+          if constexpr (FSEL != 0) {  // some block of class 0: S = X | D3 on the scalar unit, once per group
+            const u32x8 S = fold_planes(sp[0], sp[1]);
+#pragma unroll
+            for (int b = 0; b < PL_BPW; ++b) {
+              if ((FSEL >> b) & 1) pair_group_fold(pl, S, P0[b], P1[b], P2[b], am[b]);
+              else pair_group_hy<false, 2>(pl, sp[0], sp[1], P0[b], P1[b], P2[b], P3[b], nT[b], am[b], ax[b]);
+            }
+          } else
 #pragma unroll
           for (int b = 0; b < PL_BPW; ++b) {
             if (ty[b] == 0) pair_group_hy<KXS, 0>(pl, sp[0], sp[1], P0[b], P1[b], P2[b], P3[b], nT[b], am[b], ax[b]);
@@ -809,7 +895,17 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
     }
   };
   if constexpr (!KX) {
-    scan(std::false_type{});
+    // one scan loop per combination of folded blocks, chosen once per wave (no branch inside the loop)
+    using F0 = std::integral_constant<int, 0>;
+    if constexpr (FOLD) {
+      static_assert(PL_BPW == 2, "one scan instance per subset of the wave's blocks");
+      if (pure[0] && pure[1]) scan(std::false_type{}, std::integral_constant<int, 3>{});
+      else if (pure[0]) scan(std::false_type{}, std::integral_constant<int, 1>{});
+      else if (pure[1]) scan(std::false_type{}, std::integral_constant<int, 2>{});
+      else scan(std::false_type{}, F0{});
+    } else {
+      scan(std::false_type{}, F0{});
+    }
     group0();
     // The first feasible node for each tolerates value, exact, on the scalar unit (as pair_kernel):
     // in group 0, else in fn / ft; then one select per lane and block.
@@ -832,10 +928,10 @@ __global__ __launch_bounds__(W * WAVE) void pair_lds_kernel(PairArgs a) {
     bool xdone = true;
 #pragma unroll
     for (int b = 0; b < PL_BPW; ++b) xdone = xdone && __ballot(rx[b] == NOFIT) == 0;
-    if (xdone) scan(std::true_type{});
-    else scan(std::false_type{});
+    if (xdone) scan(std::true_type{}, std::integral_constant<int, 0>{});
+    else scan(std::false_type{}, std::integral_constant<int, 0>{});
   } else {  // group 0 after the scan (its registers free during it)
-    scan(std::false_type{});
+    scan(std::false_type{}, std::integral_constant<int, 0>{});
     group0();
   }
   // then the rare re-reads of a higher pair, then the decode
@@ -954,6 +1050,7 @@ hipError_t launch_pair_t(PairArgs& a, const DeviceInfo& dev, hipStream_t s) {
     const size_t bytes = (size_t)a.n_groups * GROUP_DWORDS * sizeof(uint32_t);
     const dim3 grid((unsigned)bx, (unsigned)a.nb), blk(w * WAVE);
     a.noax = dev.pair_noax >= 0 ? dev.pair_noax : (KX ? 1 : 0);
+    if (!KX && dev.pair_fold) a.noax |= PAIR_FLAG_FOLD;  // (the identity-like instances read no other bit of it)
     using PairKernel = void (*)(PairArgs);
     const PairKernel k = big ? pair_lds_kernel<SHARD, KX, PL_WAVES_BIG> : pair_lds_kernel<SHARD, KX, PL_WAVES>;
     if (bytes > 64 * 1024) {
